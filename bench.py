@@ -5,7 +5,8 @@ Metric (BASELINE.json): point-pairs/s = B*N*L / wall time of one loss evaluation
 full loss evaluation of the batch (projection + per-slice sorts + circular OT solve + reduction to per-pair losses
 and the scalar) with the clouds and directions already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: starts its N ranks itself, as child processes)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                                  (N > 1: starts its N ranks itself, as child processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
   N = 1 : BASELINE config 3 -- batch=64, N=M=2048, L=512 on one MI355X (the configuration the metric is quoted on).
@@ -16,13 +17,20 @@ and the scalar) with the clouds and directions already resident in HBM.
           collective is one RCCL all-reduce (sum) of 514 floats [512 per-pair losses | total, mean] per step.
           Total work is fixed as N grows ("scaling": "strong").
 
-Rank 0 prints ONE JSON line.  At N=1 it also carries
+Rank 0 prints ONE JSON line.  A plain run only sets up, warms up, times the K steps, writes the outputs (--dump-outputs)
+and prints the line ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", the configuration and the
+loss).  With --full the line also carries
   "roofline":     algorithmic bytes of the dominant kernel / its measured duration vs the 8 TB/s HBM peak
-  "cpu_baseline": the CPU oracle (oracle/ref_mirror.py, kind "port") timed on a bounded sample (BASELINE.md section 3:
-                  3 warm-ups, median of 5; forward and forward+backward; 1 thread and the box's CPU share), with the CPU
-                  model and the host's physical core count
+  "cpu_baseline": (N=1) the CPU oracle (oracle/ref_mirror.py, kind "port") timed on a bounded sample (BASELINE.md
+                  section 3: 3 warm-ups, median of 5; forward and forward+backward; 1 thread and the box's CPU share),
+                  with the CPU model and the host's physical core count
   "parity_rel_err": max relative difference between the GPU's per-pair losses and the CPU oracle's on the sample
-                  pairs; the process exits non-zero when it exceeds 1e-5 (a wrong-but-fast kernel prints no headline)
+                  pairs (N > 1 or --no-cpu-baseline: the first slices of the first pair); the process exits non-zero
+                  when it exceeds 1e-5 (a wrong-but-fast kernel prints no headline)
+  "mirror_ms_per_step": (N=1) the same evaluation through the drop-in Python call
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64, 64 MB at most): the
+per-pair losses, [total, mean], and rank 0's per-slice costs and optimal shifts.  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 Other modes (--mode train | chamfer | config5 | mirror) print their own single line; they are secondary figures.
 """
 from __future__ import annotations
@@ -41,6 +49,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 PARITY_TOL = 1e-5               # north_star: loss values within 1e-5 relative of the reference
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all arrays together
 
 
 def next_pow2(v):
@@ -127,6 +136,11 @@ def main():
                     help="replay the step as a hipGraph instead of launching eagerly (measured: no gain, the step is "
                          "one ~0.3 ms kernel plus one small one; kept as an option)")
     ap.add_argument("--cpu-sample-pairs", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline (kernel-only timing), CPU "
+                         "baseline, parity against the CPU oracle, timing of the drop-in Python call")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` outside torchrun: start the N ranks ourselves.  Nothing has touched the GPU yet (torch
@@ -193,20 +207,23 @@ def main():
         _lib.check(lib.shw_ssw_reduce(slice_cost.data_ptr(), Bl, Ll, 1.0 / L, out.data_ptr() + 4 * pair_lo,
                                       out.data_ptr() + 4 * B, st), "shw_ssw_reduce")
 
-    # ---- roofline of the dominant kernel (ssw_forward_kernel), HIP events on the launch stream, measured BEFORE
-    #      the timed region: it also brings the GPU to its steady-state clocks, which 5 warm-up steps of 0.3 ms do not
-    reps = max(20, min(args.steps, 200))
+    # ---- brings the GPU to its steady-state clocks, which 5 warm-up steps of 0.3 ms do not
     for _ in range(100):                     # ~25 ms of launches: the clocks are up before anything is timed
         enqueue_loss(outs[0])
     torch.cuda.synchronize(device)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(reps):
-        _lib.check(lib.shw_ssw_forward(x.data_ptr(), y.data_ptr(), U.data_ptr(), Bl, N, N, Ll, Ll * 6, p,
-                                       slice_cost.data_ptr(), slice_shift.data_ptr(), stream), "shw_ssw_forward")
-    ev1.record()
-    torch.cuda.synchronize(device)
-    kernel_ms = ev0.elapsed_time(ev1) / reps
+    # ---- --full: roofline of the dominant kernel (ssw_forward_kernel), HIP events on the launch stream, measured
+    #      BEFORE the timed region
+    kernel_ms = None
+    if args.full:
+        reps = max(20, min(args.steps, 200))
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(reps):
+            _lib.check(lib.shw_ssw_forward(x.data_ptr(), y.data_ptr(), U.data_ptr(), Bl, N, N, Ll, Ll * 6, p,
+                                           slice_cost.data_ptr(), slice_shift.data_ptr(), stream), "shw_ssw_forward")
+        ev1.record()
+        torch.cuda.synchronize(device)
+        kernel_ms = ev0.elapsed_time(ev1) / reps
 
     graph = None
     if args.graph and not multi:
@@ -277,6 +294,12 @@ def main():
         elapsed = float(t.item())
     pair_losses = out[:B].clone()
     loss_value = float(out[B].item())                     # N > 1: sum over ranks of the partial totals
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "pair_losses": pair_losses.cpu().numpy(),
+            "loss_total_mean": out[B:B + 2].cpu().numpy(),
+            "slice_costs": slice_cost[:Bl * Ll].view(Bl, Ll).cpu().numpy(),
+            "slice_shifts": slice_shift[:Bl * Ll].view(Bl, Ll).cpu().double().numpy()})
 
     ms_per_step = 1e3 * elapsed / args.steps
     log("timed region done: %.3f ms/step" % ms_per_step)
@@ -309,37 +332,11 @@ def main():
         "loss": loss_value,
     }
 
-    # clouds read once + directions + per-pair loss -- for this rank's block
-    algo_bytes = 12 * Bl * (N + N) + 24 * Bl * Ll + 4 * Bl
-    achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-    # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE/WRITE_SIZE corrected per the
-    # guide); only valid for the workload it was measured on
-    traffic = os.environ.get("SHW_BENCH_TRAFFIC_BYTES")
-    if traffic is None and (Bl, N, Ll, p) == (64, 2048, 512, 2.0):
-        for name in ("r03_traffic.json", "r02_traffic.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as fh:
-                    traffic = json.load(fh)["ssw_forward_kernel<32,1,2,true>"]["traffic_bytes"]
-                break
-            except Exception:
-                traffic = None
-    result["roofline"] = {
-        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-        "frac": achieved / HBM_PEAK_GBPS, "traffic": float(traffic) if traffic else None,
-        "kernel": "ssw_forward_kernel<32,1,2,true>" if (N, p) == (2048, 2.0) else "ssw_forward_kernel",
-        "kernel_ms": kernel_ms, "algorithmic_bytes": algo_bytes,
-        "secondary_model": {"unit": "compare-exchanges/s",
-                            "achieved": Bl * Ll * 2 * (next_pow2(N) // 2) * stages(N) / (kernel_ms * 1e-3),
-                            "note": "compare-exchanges of two bitonic sorts of next_pow2(N) keys per slice -- the unit "
-                                    "of round 1's network kernel, kept for comparison; the distribution sort of round 2 "
-                                    "does the same job with ~1/4 of them (DESIGN.md section 4)"},
-        "note": "compulsory HBM traffic is 0.06 B/point-pair: the kernel is VALU-issue / LDS bound (projection, "
-                "distribution sort through LDS, shift solve), not HBM bound; DESIGN.md section 4 has the VALU model",
-        "point_pairs_per_s_kernel_only": Bl * N * Ll / (kernel_ms * 1e-3),
-    }
+    if args.full:
+        result["roofline"] = roofline(kernel_ms, Bl, N, Ll, p)
 
     rc = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         if not multi and not args.no_cpu_baseline:
             base = cpu_baseline(x, y, U, p, args.cpu_sample_pairs)
             ref_pairs = base.pop("_pair_losses")
@@ -373,6 +370,57 @@ def main():
     if dist is not None:
         dist.destroy_process_group()
     return rc
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as path/<name>.npy in float32 or float64, 64 MB in all at most.  An array larger than
+    its share of that is replaced by a fixed, seeded sample of its flattened entries (in index order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s, not float32 / float64" % (name, a.dtype))
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            log("--dump-outputs: %s has %d entries, writing a seeded sample of %d" % (name, a.size, keep))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+    log("outputs written to %s: %s" % (path, ", ".join(sorted(arrays))))
+
+
+def roofline(kernel_ms, Bl, N, Ll, p):
+    """--full: the dominant kernel's HIP-event time against the HBM roofline, for this rank's block."""
+    # SURVEY.md 8d: clouds read once + directions + per-pair loss -- for this rank's block
+    algo_bytes = 12 * Bl * (N + N) + 24 * Bl * Ll + 4 * Bl
+    achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+    # HBM bytes per launch from the committed rocprofv3 --pmc passes (FETCH_SIZE/WRITE_SIZE corrected per the
+    # guide); only valid for the workload it was measured on
+    traffic = os.environ.get("SHW_BENCH_TRAFFIC_BYTES")
+    if traffic is None and (Bl, N, Ll, p) == (64, 2048, 512, 2.0):
+        for name in ("r03_traffic.json", "r02_traffic.json"):
+            try:
+                with open(os.path.join(ROOT, "profiles", name)) as fh:
+                    traffic = json.load(fh)["ssw_forward_kernel<32,1,2,true>"]["traffic_bytes"]
+                break
+            except Exception:
+                traffic = None
+    return {
+        "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+        "frac": achieved / HBM_PEAK_GBPS, "traffic": float(traffic) if traffic else None,
+        "kernel": "ssw_forward_kernel<32,1,2,true>" if (N, p) == (2048, 2.0) else "ssw_forward_kernel",
+        "kernel_ms": kernel_ms, "algorithmic_bytes": algo_bytes,
+        "secondary_model": {"unit": "compare-exchanges/s",
+                            "achieved": Bl * Ll * 2 * (next_pow2(N) // 2) * stages(N) / (kernel_ms * 1e-3),
+                            "note": "compare-exchanges of two bitonic sorts of next_pow2(N) keys per slice -- the unit "
+                                    "of round 1's network kernel, kept for comparison; the distribution sort of round 2 "
+                                    "does the same job with ~1/4 of them (DESIGN.md section 4)"},
+        "note": "compulsory HBM traffic is 0.06 B/point-pair: the kernel is VALU-issue / LDS bound (projection, "
+                "distribution sort through LDS, shift solve), not HBM bound; DESIGN.md section 4 has the VALU model",
+        "point_pairs_per_s_kernel_only": Bl * N * Ll / (kernel_ms * 1e-3),
+    }
 
 
 def self_launch(gpus):
@@ -435,24 +483,28 @@ def side_modes(args, shw, B, N, L, device):
         def step():
             xs.grad = None
             ys.grad = None
-            shw.sliced_cost(xs, ys, U, p=p).backward()
+            val = shw.sliced_cost(xs, ys, U, p=p)
+            val.backward()
+            return {"loss": val.detach(), "grad_x": xs.grad, "grad_y": ys.grad}
         unit, per_step = "point-pairs/s (forward + input gradients)", B * N * L
     elif args.mode == "mirror":
         def step():
-            shw.sliced_cost(x, y, U, p=p)
+            return {"loss": shw.sliced_cost(x, y, U, p=p)}
         unit, per_step = "point-pairs/s (forward through the drop-in Python call)", B * N * L
     else:
         def step():
-            shw.chamfer_distance(x, y)
+            return {"loss": shw.chamfer_distance(x, y)[0]}
         unit, per_step = "pair-distances/s (both directions)", 2 * B * N * N
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outputs = step()
     torch.cuda.synchronize(device)
     el = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: v.detach().float().cpu().numpy() for k, v in outputs.items()})
     print(json.dumps({"metric": args.mode, "value": per_step / el, "unit": unit, "ms_per_step": 1e3 * el,
                       "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "dtype": "f32",
                       "config": {"workload": "B=%d N=%d L=%d p=%g" % (B, N, L, p)}}), flush=True)

@@ -81,3 +81,23 @@ def test_bench_gpus_2_starts_its_ranks_and_fails_only_at_device_selection():
     assert "starting 2 ranks" in res.stderr
     assert "No HIP GPUs are available" in res.stderr
     assert res.stdout.strip() == ""                      # no JSON line from a failed run
+
+
+def test_bench_dump_outputs_caps_the_size_with_a_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 only, and an array larger than its share of the 64 MB cap is written as
+    the same seeded sample of its entries every time."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    small = np.arange(10, dtype=np.float64)
+    big = np.random.default_rng(1).standard_normal((64, 100)).astype(np.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"small": small, "big": big})
+    assert np.array_equal(np.load(str(tmp_path / "a" / "small.npy")), small)
+    a, b = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert a.dtype == np.float32 and a.nbytes == 2048 and np.array_equal(a, b)
+    assert np.isin(a, big).all()
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "c"), {"shift": np.zeros(3, dtype=np.int32)})

@@ -205,7 +205,7 @@ def test_bench_self_launch_path_prints_one_json_line():
     env = dict(os.environ, SHW_BENCH_FORCE_SPAWN="1")
     env.pop("WORLD_SIZE", None)
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, env=env)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, cwd=ROOT, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = res.stdout.strip().split("\n")
     assert len(lines) == 1, lines

@@ -887,7 +887,7 @@ def _run_bench(extra, torchrun=False):
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    d = _run_bench(["--cpu-sample-pairs", "1"])
+    d = _run_bench(["--full", "--cpu-sample-pairs", "1"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -901,8 +901,49 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
 
 
 def test_bench_under_torchrun_uses_rccl_and_still_prints_one_line():
-    d = _run_bench(["--no-cpu-baseline"], torchrun=True)
+    d = _run_bench(["--full", "--no-cpu-baseline"], torchrun=True)
     assert d["n_gpus"] == 1 and "roofline" in d and "cpu_baseline" not in d
+
+
+def test_bench_plain_run_times_only_the_headline():
+    """Without --full the line carries the headline figure and nothing that needs runs of its own."""
+    d = _run_bench([])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "loss"):
+        assert key in d, key
+    assert d["steps"] == 20 and d["warmup"] == 5 and d["unit"] == "point-pairs/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["ms_per_step"] > 0
+    assert abs(d["value"] - 64 * 2048 * 512 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for key in ("roofline", "cpu_baseline", "parity_rel_err", "mirror_ms_per_step"):
+        assert key not in d, key
+
+
+def test_bench_dump_outputs_are_the_losses_of_the_seeded_inputs(shw, tmp_path):
+    """--dump-outputs writes what the last timed step computed; the inputs are seeded, so two runs write the same
+    arrays, and they are the library's losses of bench.py's own clouds and directions."""
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--batch", "4", "--points", "1000", "--slices", "24"]
+    dumps = []
+    for run in ("a", "b"):
+        d = _run_bench(args + ["--dump-outputs", str(tmp_path / run)])
+        assert d["config"]["global_batch"] == 4 and d["config"]["slices"] == 24
+        dumps.append({k: np.load(str(tmp_path / run / (k + ".npy"))) for k in
+                      ("pair_losses", "loss_total_mean", "slice_costs", "slice_shifts")})
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert a["pair_losses"].shape == (4,) and a["slice_costs"].shape == (4, 24) and a["slice_shifts"].shape == (4, 24)
+    assert np.allclose(a["pair_losses"], a["slice_costs"].astype(np.float64).mean(1), rtol=1e-6)
+    assert np.allclose(a["loss_total_mean"], [a["pair_losses"].sum(), a["pair_losses"].mean()], rtol=1e-6)
+    sys.path.insert(0, root)
+    import bench
+    x, y = bench.make_clouds(4, 1000, "cuda")
+    U = bench.make_directions(shw, 4, 24, "cuda")
+    pair, cost, shift = shw.ssw_pair_losses(x, y, U, p=2, return_slices=True)
+    assert np.allclose(a["slice_costs"], cost.cpu().numpy(), rtol=1e-6, atol=0)
+    assert np.array_equal(a["slice_shifts"], shift.cpu().double().numpy())
+    assert np.allclose(a["pair_losses"], pair.cpu().numpy(), rtol=1e-6, atol=0)
 
 
 def test_dist_module_over_rccl_with_the_hip_evaluator():

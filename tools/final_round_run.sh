@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/final
 mkdir -p $OUT
 cd $ROOT
 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1; echo "tests rc=$?"; tail -2 $OUT/gpu_tests.log
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cat $OUT/bench_default.json
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "bench rc=$?"; cat $OUT/bench_default.json
 for mode in train mirror chamfer config5; do
   python bench.py --mode $mode --no-cpu-baseline > $OUT/bench_$mode.json 2> $OUT/bench_$mode.err; echo "bench $mode rc=$?"; cut -c1-400 $OUT/bench_$mode.json
 done

@@ -11,8 +11,8 @@ has() { [[ " $PARTS " == *" $1 "* ]]; }
 
 if has bench; then
   echo "== bench.py, the driver's arguments and the defaults"
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.log || tail -5 $OUT/bench_driver_args.log
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.log || tail -5 $OUT/bench_default.log
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.log || tail -5 $OUT/bench_driver_args.log
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.log || tail -5 $OUT/bench_default.log
   cut -c1-400 $OUT/bench_driver_args.json
 fi
 if has headline; then
@@ -57,8 +57,8 @@ fi
 if has nonuniform; then
   echo "== clouds that are not uniform in angle (ADVICE r2)"
   timeout -k 10 200 python3 tools/nonuniform_time.py 2>&1 | grep -v amdgpu.ids > $OUT/nonuniform.txt
-  if [ -f gpurun_variants/fwd_runlen.so ]; then
-    SHW_RUNLEN=1 SHW_LIB_PATH=$ROOT/gpurun_variants/fwd_runlen.so timeout -k 10 200 python3 tools/nonuniform_time.py 2>&1 | grep -v amdgpu.ids >> $OUT/nonuniform.txt
+  if [ -f build/variants/fwd_runlen.so ]; then
+    SHW_RUNLEN=1 SHW_LIB_PATH=$ROOT/build/variants/fwd_runlen.so timeout -k 10 200 python3 tools/nonuniform_time.py 2>&1 | grep -v amdgpu.ids >> $OUT/nonuniform.txt
   fi
   cat $OUT/nonuniform.txt
 fi
