@@ -176,6 +176,23 @@ SHW_API int shw_esw_backward_points(const float* thetas, const float* coef_s, co
 SHW_API int shw_esw_backward_dirs(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
                           const float* slice_w, int pairs, int n, int slices, float* grad_thetas, void* stream);
 
+/* The same three entries for points of dimension `dim`, 1 <= dim <= 64 (the notebooks' ASWD projects points
+ * augmented to 6 coordinates): xs, xt (pairs, n, dim); thetas (slices, dim) shared (theta_pair_stride = 0) or
+ * (pairs, slices, dim) (stride >= slices*dim); grad_xs / grad_xt (pairs, n, dim); grad_thetas (pairs, slices, dim).
+ * Keys are sum_d x[i,d] * theta[l,d] accumulated in the order d = 0..dim-1; coef_s / coef_t as above.  n <= 4096,
+ * pairs <= 65535 in the backward entries.  Gradients are reduced in a fixed order (no atomics). */
+SHW_API int shw_esw_forward_dim(const float* xs, const float* xt, const float* thetas, int pairs, int n, int dim,
+                                int slices, long theta_pair_stride, float p, float* slice_sum, float* coef_s,
+                                float* coef_t, void* stream);
+
+SHW_API int shw_esw_backward_points_dim(const float* thetas, const float* coef_s, const float* coef_t,
+                                        const float* slice_w, int pairs, int n, int dim, int slices,
+                                        long theta_pair_stride, float* grad_xs, float* grad_xt, void* stream);
+
+SHW_API int shw_esw_backward_dirs_dim(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
+                                      const float* slice_w, int pairs, int n, int dim, int slices, float* grad_thetas,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Log-domain Sinkhorn distance (comparison metric); value-only entry point.
  * Replaces: log_Sinkhorn_Distance_Loss.forward and log_N_Sinkhorn_Distance_Loss.forward

@@ -47,16 +47,6 @@ __device__ __forceinline__ void load_projections(const float* __restrict__ X, in
   }
 }
 
-// order-preserving map float -> unsigned (negative floats included), for the key+index items
-__device__ __forceinline__ float orderable(float x) {
-  const int b = as_i(x);
-  return as_f(b ^ ((b >> 31) | (int)0x80000000));
-}
-__device__ __forceinline__ float from_orderable(float x) {
-  const int b = as_i(x);
-  return as_f(b ^ (((~b) >> 31) | (int)0x80000000));
-}
-
 template <int EPT, int WAVES, int PMODE, bool GRAD>
 __global__ __launch_bounds__(WAVES * 64) void esw_kernel(EswArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];

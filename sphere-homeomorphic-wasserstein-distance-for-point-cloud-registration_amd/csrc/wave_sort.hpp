@@ -112,6 +112,16 @@ __device__ __forceinline__ item_t make_item(float key, int idx) {
 __device__ __forceinline__ float item_key(item_t it) { return as_f((int)(it >> 32)); }
 __device__ __forceinline__ int item_idx(item_t it) { return (int)(unsigned)it; }
 
+// order-preserving map float -> unsigned (negative floats included), for the key+index items of the Euclidean kernels
+__device__ __forceinline__ float orderable(float x) {
+  const int b = as_i(x);
+  return as_f(b ^ ((b >> 31) | (int)0x80000000));
+}
+__device__ __forceinline__ float from_orderable(float x) {
+  const int b = as_i(x);
+  return as_f(b ^ (((~b) >> 31) | (int)0x80000000));
+}
+
 template <int MASK>
 __device__ __forceinline__ item_t lane_xor(item_t x, int lane) {
   const float lo = lane_xor<MASK>(as_f((int)(unsigned)x), lane);
