@@ -5,11 +5,13 @@
 // 66 stages x 32 keys = 2112 slow-rate instructions + 672 crossbar moves per 2048-key sort, and two of them are
 // 70 % of the loss kernel.  Circle coordinates are numbers in [0, 1] -- a key's value says where it belongs:
 //
-//   1. histogram   b = min(floor(key * NB), NB-1);  rank = ds_add_rtn(cnt[b], 1)        (NB = 32*EPT bins: 2 keys per
+//   1. histogram   b = min(floor(key * NB), NB-1);  ds_add(cnt[b], 1)                     (NB = 32*EPT bins: 2 keys per
 //                                                                                          bin on average)
 //   2. scan        exclusive prefix sum over the NB counters (16 per lane in-lane, then a wave scan); the largest
 //                  counter g is the longest run of keys that share a bin
-//   3. scatter     buf[start[b] + rank] = key          (keys are now ordered by bin; inside a bin in arrival order)
+//   3. scatter     b recomputed; buf[ds_add_rtn(start[b], 1)] = key   (keys are now ordered by bin; inside a bin in
+//                  arrival order).  No per-key word lives from 1 to 3: the one-wave loss kernel sorts the target while
+//                  it holds the sorted source in registers, and a rank per key beside both made it spill.
 //   4. read back   32 consecutive positions per lane (sorted position of x[r] in lane `lane` is lane*EPT + r, the
 //                  layout wave_sort leaves)
 //   5. fix-up      g phases of odd-even transposition (in-lane compare-exchanges + one exchange across each lane
@@ -80,11 +82,20 @@ __device__ __forceinline__ int wave_inclusive_scan_dpp(int v) {
   return v;
 }
 
-// Steps 1-2.  Returns the longest equal-bin run g (wave-uniform); on return cnt[] holds the exclusive prefix sums and
-// w[r] = (rank << 16) | bin for live keys.  `n` = number of live keys; key[r] belongs to point r*64 + lane.
+// bin of a key: v_cvt_u32_f32 saturates (NaN -> 0, +inf -> 0xffffffff), so the bin is always inside [0, NB).  The
+// histogram and the placement both compute it with this one function: a key lands in the bin it was counted in.
+template <int NB>
+__device__ __forceinline__ unsigned binsort_bin(float key) {
+  const unsigned t = (unsigned)(key * (float)NB);
+  return t < (unsigned)(NB - 1) ? t : (unsigned)(NB - 1);
+}
+
+// Steps 1-2.  Returns the longest equal-bin run g (wave-uniform); on return cnt[] holds the exclusive prefix sums (the
+// first sorted position of every bin).  `n` = number of live keys; key[r] belongs to point r*64 + lane.  Nothing per key
+// survives the counting pass (no rank is returned): binsort_place recomputes the bin and takes the position from an
+// atomic on the scanned starts, so the sorted source carried across the target's sort is the only per-key state.
 template <int EPT, bool FULL>
-__device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], unsigned (&w)[EPT], int lane, int n,
-                                                 unsigned* cnt) {
+__device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], int lane, int n, unsigned* cnt) {
   constexpr int NB = binsort_bins<EPT>();
   constexpr int BPL = NB / 64;                          // bins per lane in the scan (EPT/2: 16 at EPT = 32)
   static_assert(BPL >= 4 && BPL % 4 == 0, "bin sort needs >= 4 bins per lane");
@@ -93,7 +104,7 @@ __device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], unsign
   for (int j = 0; j < BPL / 4; ++j)
     *reinterpret_cast<u32x4*>(cnt + j * 256 + lane * 4) = u32x4{0u, 0u, 0u, 0u};
   __builtin_amdgcn_wave_barrier();
-  constexpr int CH = chunk_of(EPT);                      // atomics in flight per lane; bounds the live registers
+  constexpr int CH = chunk_of(EPT);                      // rows per chunk (the placement's atomics in flight per lane)
 #pragma unroll
   for (int r0 = 0; r0 < EPT; r0 += CH) {
     // key[r] belongs to point r*64 + lane: the pads of a class that is not full are its LAST rows -- a chunk of rows is
@@ -106,38 +117,20 @@ __device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], unsign
     const bool all_live = FULL || (kByChunk && (r0 + CH) * kWave <= n);
     const bool none_live = !FULL && kByChunk && r0 * kWave >= n;
     if (none_live) {
-#pragma unroll
-      for (int j = 0; j < CH; ++j) w[r0 + j] = 0u;
+      // nothing to count: the placement puts these pads at their own index
     } else if (all_live) {
-      unsigned b[CH], rank[CH];
 #pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        // v_cvt_u32_f32 saturates (NaN -> 0, +inf -> 0xffffffff): the bin is always inside [0, NB)
-        const unsigned t = (unsigned)(key[r0 + j] * (float)NB);
-        b[j] = t < (unsigned)(NB - 1) ? t : (unsigned)(NB - 1);
-      }
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-        rank[j] = __hip_atomic_fetch_add(cnt + b[j], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#pragma unroll
-      for (int j = 0; j < CH; ++j) w[r0 + j] = (rank[j] << 16) | b[j];
+      for (int j = 0; j < CH; ++j)                       // result unused: ds_add_u32, nothing to wait for
+        __hip_atomic_fetch_add(cnt + binsort_bin<NB>(key[r0 + j]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     } else {
-      unsigned b[CH], rank[CH];
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
-        const unsigned t = (unsigned)(key[r0 + j] * (float)NB);
-        b[j] = t < (unsigned)(NB - 1) ? t : (unsigned)(NB - 1);
-        // pads (they add 0) go to 64 different counters: 64 atomics on ONE address would be served one after the other
-        b[j] = ((r0 + j) * kWave + lane < n) ? b[j] : (unsigned)lane;
+        const bool live = (r0 + j) * kWave + lane < n;
+        // pads add 0 (no divergent branch around the atomic), to 64 different counters: 64 atomics on ONE address would
+        // be served one after the other
+        __hip_atomic_fetch_add(cnt + (live ? binsort_bin<NB>(key[r0 + j]) : (unsigned)lane), live ? 1u : 0u,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       }
-#pragma unroll
-      for (int j = 0; j < CH; ++j) {
-        // pads add 0: no divergent branch around the atomic
-        const unsigned inc = ((r0 + j) * kWave + lane < n) ? 1u : 0u;
-        rank[j] = __hip_atomic_fetch_add(cnt + b[j], inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-      }
-#pragma unroll
-      for (int j = 0; j < CH; ++j) w[r0 + j] = (rank[j] << 16) | b[j];
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -186,10 +179,12 @@ __device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
   x[0] = lo;
 }
 
-// Steps 3-5 (only after binsort_histogram returned g <= SHW_BINSORT_MAX_RUN).
+// Steps 3-5 (only after binsort_histogram returned g <= SHW_BINSORT_MAX_RUN).  The position of a live key is what
+// ds_add_rtn returns on its bin's scanned start (cnt[] holds the bin ends afterwards); inside a bin the keys land in the
+// order the atomics are served, which the fix-up phases make irrelevant.
 template <int EPT, bool FULL>
-__device__ __forceinline__ void binsort_place(float (&key)[EPT], const unsigned (&w)[EPT], int lane, int n, int g,
-                                              const unsigned* cnt, float* buf) {
+__device__ __forceinline__ void binsort_place(float (&key)[EPT], int lane, int n, int g, unsigned* cnt, float* buf) {
+  constexpr int NB = binsort_bins<EPT>();
   char* bytes = reinterpret_cast<char*>(buf);
   constexpr int CH = chunk_of(EPT);
 #pragma unroll
@@ -202,15 +197,26 @@ __device__ __forceinline__ void binsort_place(float (&key)[EPT], const unsigned 
 #pragma unroll
       for (int j = 0; j < CH; ++j)
         *reinterpret_cast<float*>(bytes + binsort_addr<EPT>((unsigned)((r0 + j) * kWave + lane))) = key[r0 + j];
-    } else {
-      unsigned start[CH];
+    } else if (all_live) {
+      unsigned pos[CH];
 #pragma unroll
-      for (int j = 0; j < CH; ++j) start[j] = cnt[w[r0 + j] & 0xffffu];
+      for (int j = 0; j < CH; ++j)
+        pos[j] = __hip_atomic_fetch_add(cnt + binsort_bin<NB>(key[r0 + j]), 1u, __ATOMIC_RELAXED,
+                                        __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+      for (int j = 0; j < CH; ++j) *reinterpret_cast<float*>(bytes + binsort_addr<EPT>(pos[j])) = key[r0 + j];
+    } else {
+      unsigned pos[CH];
+#pragma unroll
+      for (int j = 0; j < CH; ++j) {
+        const bool live = (r0 + j) * kWave + lane < n;
+        pos[j] = __hip_atomic_fetch_add(cnt + (live ? binsort_bin<NB>(key[r0 + j]) : (unsigned)lane), live ? 1u : 0u,
+                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      }
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const unsigned i = (unsigned)((r0 + j) * kWave + lane);
-        const unsigned pos = (all_live || (int)i < n) ? start[j] + (w[r0 + j] >> 16) : i;
-        *reinterpret_cast<float*>(bytes + binsort_addr<EPT>(pos)) = key[r0 + j];
+        *reinterpret_cast<float*>(bytes + binsort_addr<EPT>((int)i < n ? pos[j] : i)) = key[r0 + j];
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -263,10 +269,9 @@ __device__ __forceinline__ void wave_sort_relayout(T (&key)[EPT], int lane, T ma
 template <int EPT, bool FULL>
 __device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* counters, float* buf) {
   unsigned* cnt = reinterpret_cast<unsigned*>(counters);
-  unsigned w[EPT];
-  const int g = binsort_histogram<EPT, FULL>(key, w, lane, n, cnt);
+  const int g = binsort_histogram<EPT, FULL>(key, lane, n, cnt);
   if (g <= SHW_BINSORT_MAX_RUN) {
-    binsort_place<EPT, FULL>(key, w, lane, n, g, cnt, buf);
+    binsort_place<EPT, FULL>(key, lane, n, g, cnt, buf);
   } else {
 #ifndef SHW_ABL_NO_FALLBACK
     if constexpr (is_pow2(EPT)) wave_sort<EPT>(key, lane);

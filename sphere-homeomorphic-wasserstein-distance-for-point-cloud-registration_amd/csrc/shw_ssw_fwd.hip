@@ -81,7 +81,9 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
       part += key[r];
     }
 #else
-    const float part = load_coords<EPT, FULL>(X, count, ln, U, key);
+    // the full 32-keys-per-lane class loads 16 points per chunk (48 loads in flight per lane): the registers are there
+    // since the sort keeps no per-key words (0.2092 -> 0.2070 ms per step at config 3; the other classes keep 8)
+    const float part = load_coords<EPT, FULL, false, kWave, false, (EPT == 32 && FULL) ? 16 : 8>(X, count, ln, U, key);
 #endif
 #ifdef SHW_DBG_RUNLEN          // developer build (tools/nonuniform_time.py): slice_shift reports the longest equal-bin run
     if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL>(key, ln, count, scratch));
@@ -111,7 +113,7 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 #else
   int k;
   if constexpr (FULL || !BINS) {
-    k = solve_shift<EPT, PMODE, FULL>(u, vbuf, lane, A.n, sum_u, sum_v, A.p, A.p_int, best);
+    k = solve_shift<EPT, PMODE, FULL, true>(u, vbuf, lane, A.n, sum_u, sum_v, A.p, A.p_int, best);
   } else {
     // any n: pre-rotated extended rows over the sort's scratch (counters + staging buffer are dead), target kept in
     // registers for the rare rewrite
@@ -300,7 +302,7 @@ int dispatch_forward2(SswArgs& A, hipStream_t stream);           // shw_ssw_fwd2
 
 // Which loss-only kernel serves p != 1 (measured, profiles/r02_ab_twowave_fwd.txt):
 //   n == m == 2048 exactly    : one wave per slice (ssw_forward_kernel, in-wave distribution sort) -- 0.228 ms at config 3
-//                               against 0.240 for two waves, at the price of 25 spilled VGPRs
+//                               against 0.240 for two waves (round 4: 0.207, and no longer spilling)
 //   512..2048 (padded) points : otherwise two waves per slice, one cloud each (shw_ssw_fwd2.hip): no spills, and faster
 //                               wherever the cloud does not fill its size class (N=2000: 0.306 vs 0.330 ms)
 //   > 2048                    : W = padded / 2048 waves per slice, cooperative distribution sort (shw_ssw_coop.hip)

@@ -227,6 +227,33 @@ __device__ __forceinline__ void shift_costs3(const float (&u)[NR], const float* 
   cp = wave_sum_uniform(sp, lane & 63);
 }
 
+// c(kk) alone, as shift_costs3 forms each of its three sums: the term of register j reads the same target position
+// e0 + j + kk (for every live j) and is added in the same order, then the same wave_sum_uniform -- so the result has
+// the bits of the cm / c0 / cp that a three-shift evaluation at kk + 1 / kk / kk - 1 returns.  solve_shift uses it after a
+// unit step, where two of the three costs are already known.
+template <int EPT, int PMODE, int NCOL = 64, int NR = EPT>
+__device__ __forceinline__ float shift_cost1(const float (&u)[NR], const float* vbuf, int lane, int n, int kk, float p,
+                                             int p_int, int r_base = 0) {
+  float s = 0.f;
+  const int e0 = lane * EPT + r_base;
+  const int last = n - 1;
+  constexpr int CH = chunk_of(NR);
+#pragma unroll
+  for (int r0 = 0; r0 < NR; r0 += CH) {
+    float v[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) v[j] = target_unrolled<EPT, NCOL>(vbuf, min(e0 + r0 + j, last) + kk, n);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      const bool live = (e0 + r0 + j) < n;
+      const float a = pow_abs<PMODE>(u[r0 + j] - v[j], p, p_int);
+      s += live ? a : 0.f;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return wave_sum_uniform(s, lane & 63);
+}
+
 // one fetch of shift_costs3_inc (arguments by value: as captured references the offsets end up as a table in scratch
 // memory read through flat pointers)
 __device__ __forceinline__ float inc_fetch(const char* row, bool before_turn, bool first_column, int a0, int a1, int b0,
@@ -361,9 +388,49 @@ __device__ __forceinline__ void shift_costs3_full(const float (&u)[NR], const fl
   cp = wave_sum_uniform(sp, lane & 63);
 }
 
+// c(kk) alone for n == 64*EPT (shift_cost1 in the addressing of shift_costs3_full): the window starts at kk instead of
+// k - 1 and is EPT long, so the carry is 0 or 1.  A position's (column, row, turn) do not depend on where the window
+// starts: the terms, their order and the reduction are those of the three-shift form.
+template <int EPT, int PMODE, int NCOL = 64, int NR = EPT>
+__device__ __forceinline__ float shift_cost1_full(const float (&u)[NR], const float* vbuf, int lane, int kk, float p,
+                                                  int p_int, int r_base = 0) {
+  constexpr int LOG = __builtin_ctz(EPT);
+  const int base = kk + r_base;
+  const int kl = base & (EPT - 1);
+  const int kh = base >> LOG;
+  int addr[2];
+  float turn[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = lane + kh + c;
+    addr[c] = (col & (NCOL - 1)) << 2;
+    turn[c] = (float)(col >> __builtin_ctz(NCOL));
+  }
+  const char* rows = reinterpret_cast<const char*>(vbuf);
+  auto fetch = [&](int j) -> float {                            // j compile-time after unrolling
+    const int rj = kl + j;                                      // scalar
+    const bool carry = rj >= EPT;
+    return *reinterpret_cast<const float*>(rows + (carry ? addr[1] : addr[0]) + (rj & (EPT - 1)) * (NCOL * 4)) +
+           (carry ? turn[1] : turn[0]);
+  };
+  float s = 0.f;
+  constexpr int CH = NR < 8 ? NR : 8;
+#pragma unroll
+  for (int r0 = 0; r0 < NR; r0 += CH) {
+    float v[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j) v[j] = fetch(r0 + j);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) s += pow_abs<PMODE>(u[r0 + j] - v[j], p, p_int);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return wave_sum_uniform(s, lane & 63);
+}
+
 // Minimise the convex sequence c(k), |k| <= n (theta in [-1, 1], the reference's bracket :174-177).
 // Returns k*, writes c(k*) (sum form).
-template <int EPT, int PMODE, bool FULL = false>
+// REUSE: evaluate only the new shift after a unit step (the loss kernel; the training kernels keep three per step).
+template <int EPT, int PMODE, bool FULL = false, bool REUSE = false>
 __device__ __forceinline__ int solve_shift(const float (&u)[EPT], const float* vbuf, int lane, int n,
                                            float sum_u, float sum_v, float p, int p_int, float& best) {
   int lo = -n, hi = n;
@@ -372,15 +439,32 @@ __device__ __forceinline__ int solve_shift(const float (&u)[EPT], const float* v
   int k = __builtin_amdgcn_readfirstlane((int)guess);         // k lives in an SGPR from here on
   bool lo_tight = false, hi_tight = false;
   int step = 1;
-  float cm, c0, cp;
+  float cm = 0.f, c0 = 0.f, cp = 0.f;
+  // a unit step (the first gallop step, or a bisection that lands next door) already knows two of its three costs:
+  // c(k -/+ 1) and c(k) are the c(k) and c(k +/- 1) of the evaluation before, bit for bit (shift_cost1).  The
+  // incremental evaluation of the small partial classes (shift_costs3_inc) has no one-shift form and always takes three.
+  constexpr bool kReuse = REUSE && (FULL || !(SHW_SOLVE_INC && EPT <= 16));
+  int kprev = k + 2;                   // no unit step before the first evaluation
   // every iteration removes k from [lo, hi]; galloping doubles, bisection halves: <= ~2 log2(2n)+2
   // iterations.  The hard cap only guards against non-finite input (comparisons all false -> exit).
   for (int it = 0; it < 64; ++it) {
     int ln = lane;                       // opaque copy: no lane-derived constants held across iterations
     asm volatile("" : "+v"(ln));
-    if constexpr (FULL) shift_costs3_full<EPT, PMODE>(u, vbuf, ln, k, p, p_int, cm, c0, cp);
-    else if constexpr (SHW_SOLVE_INC && EPT <= 16) shift_costs3_inc<EPT, PMODE>(u, vbuf, ln, n, k, p, p_int, cm, c0, cp);
-    else shift_costs3<EPT, PMODE>(u, vbuf, ln, n, k, p, p_int, cm, c0, cp);   // (diagnostic one-wave kernels of the big classes)
+    const int d = k - kprev;             // wave-uniform
+    if (kReuse && (d == 1 || d == -1)) {
+      float c;
+      if constexpr (FULL) c = shift_cost1_full<EPT, PMODE>(u, vbuf, ln, k + d, p, p_int);
+      else c = shift_cost1<EPT, PMODE>(u, vbuf, ln, n, k + d, p, p_int);
+      if (d == 1) { cm = c0; c0 = cp; cp = c; }
+      else { cp = c0; c0 = cm; cm = c; }
+    } else if constexpr (FULL) {
+      shift_costs3_full<EPT, PMODE>(u, vbuf, ln, k, p, p_int, cm, c0, cp);
+    } else if constexpr (SHW_SOLVE_INC && EPT <= 16) {
+      shift_costs3_inc<EPT, PMODE>(u, vbuf, ln, n, k, p, p_int, cm, c0, cp);
+    } else {
+      shift_costs3<EPT, PMODE>(u, vbuf, ln, n, k, p, p_int, cm, c0, cp);   // (diagnostic one-wave kernels of the big classes)
+    }
+    kprev = k;
     const bool right = (cp < c0) && (k < hi);
     const bool left = !right && (cm < c0) && (k > lo);
     if (!right && !left) break;
@@ -562,7 +646,8 @@ __device__ __forceinline__ int solve_shift_ext(const float (&u)[EPT], const floa
 // NCOL: lanes that share the cloud (64 for one wave; 64*W when W waves of a workgroup own a slice together, `lane`
 // then being the index among those lanes): lane owns points r*NCOL + lane.
 // FOLD: how the masked classes take coordinate-row mode, see below.
-template <int EPT, bool FULL = false, bool CHAINED = false, int NCOL = kWave, bool FOLD = false>
+// MOST: most points per lane whose loads are issued together (the chunk of the projection loop).
+template <int EPT, bool FULL = false, bool CHAINED = false, int NCOL = kWave, bool FOLD = false, int MOST = 8>
 __device__ __forceinline__ float load_coords(const float* __restrict__ X, int count, int lane,
                                              const float (&U)[6], float (&key)[EPT], int live_count = -1) {
   // `count` bounds the addresses (clamp), `live_count` (default: count) says how many of the 64*EPT slots are
@@ -590,7 +675,7 @@ __device__ __forceinline__ float load_coords(const float* __restrict__ X, int co
   }
   const int wide = (kFold && rows) ? 0 : -1;       // all ones: 12-byte records
   const int o1 = (kFold && rows) ? 0 : 1, o2 = (kFold && rows) ? 0 : 2;
-  constexpr int CH = chunk_of(EPT);                // 8 points (24 loads) in flight per lane (4 or 5 for the odd classes)
+  constexpr int CH = chunk_of(EPT, MOST);          // 8 points (24 loads) in flight per lane (4 or 5 for the odd classes)
 #pragma unroll
   for (int r0 = 0; r0 < EPT; r0 += CH) {
     if constexpr (!FULL && !kFold) {
