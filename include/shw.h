@@ -15,6 +15,8 @@
  *     arguments / unsupported size, anything else = the launch error.
  *   - clouds are fp32 row-major (pairs, points, 3); directions are fp32 (slices, 3, 2) orthonormal
  *     2-frames, either one set per pair (u_pair_stride = slices*6) or shared (u_pair_stride = 0).
+ *   - the entries whose names end in _f64 take the same arrays as `double` (equal cloud sizes, uniform weights, at
+ *     most SHW_MAX_POINTS_F64 points per cloud); every other entry is fp32.
  */
 #ifndef SHW_H
 #define SHW_H
@@ -32,6 +34,7 @@ extern "C" {
 #define SHW_ABI_VERSION 3 /* 2: shw_ssw_backward_points takes per-pair upstream weights; 3: shw_circle_ot takes `method`,
                              shw_sinkhorn_forward_train takes plan / cost_matrix */
 #define SHW_MAX_POINTS 8192 /* per cloud, per pair */
+#define SHW_MAX_POINTS_F64 4096 /* per cloud, per pair, on the float64 entry points (shw_*_f64) */
 
 /* ABI version of the loaded library (== SHW_ABI_VERSION of the header it was built from). */
 SHW_API int shw_abi_version(void);
@@ -149,6 +152,54 @@ SHW_API int shw_ssw_forward_general(const float* xs, const float* xt, const floa
 SHW_API int shw_circle_ot(const float* u, const float* v, const float* wu, const float* wv, long wu_row_stride,
                           long wv_row_stride, int rows, int n, int m, float p, int method, float* cost, float* aux,
                           float* grad_u, float* grad_v, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Float64 path: equal cloud sizes, uniform weights, any p >= 1 (additive to ABI 3).
+ * The reference takes its arithmetic type from its input (`dtype = u_values.dtype`, max_spherical_sliced_w.py:153-160;
+ * _fast.py:157, :221): double clouds and double directions give a double loss and double gradients.  These entries are
+ * that call: the conventions of the header comment with `double` in place of fp32, kernels of their own
+ * (csrc/shw_ssw_f64.hip: one workgroup per (pair, slice), double atan2, every sum in a fixed order -- results are
+ * bit-identical from run to run).  n == m is required and 1 <= n <= SHW_MAX_POINTS_F64; anything else returns 1.
+ * Weighted and unequal-size clouds stay on the fp32 entry points.
+ */
+
+/* Largest point count per cloud the float64 entry points accept (SHW_MAX_POINTS_F64). */
+SHW_API int shw_max_points_f64(void);
+
+/* Replaces: `U, _ = torch.linalg.qr(Z)` (max_spherical_sliced_w.py:308, _fast.py:318) on double Z, as
+ * shw_stiefel_frames: Householder steps with LAPACK's sign convention, one thread per (3, 2) matrix. */
+SHW_API int shw_stiefel_frames_f64(const double* z, long count, double* u, void* stream);
+
+/* Replaces: sliced_cost on double tensors up to, not including, the mean over slices (max_spherical_sliced_w.py:251-286,
+ * _fast.py:258-295; binary_search_circle :117-207 for p != 1 as min over shifts k of c(k), emd1D_circle :210-247 for
+ * p == 1) -- shw_ssw_forward and shw_ssw_forward_grad in one entry.
+ *   slice_cost (pairs*slices) out; slice_shift (pairs*slices) int32 out, may be NULL: k* (p != 1) or median level (p == 1);
+ *   coef_s, coef_t (pairs*slices*n) double scratch, both NULL for a loss-only call: d cost(b,l) / d coord in ORIGINAL
+ *   point order, the input of shw_ssw_backward_points_f64. */
+SHW_API int shw_ssw_forward_f64(const double* xs, const double* xt, const double* dirs, int pairs, int n, int m,
+                                int slices, long u_pair_stride, double p, double* slice_cost, int32_t* slice_shift,
+                                double* coef_s, double* coef_t, void* stream);
+
+/* Replaces: autograd through gather -> sort -> atan2 -> normalize -> matmul (:163-164, :270-279) on double tensors, as
+ * shw_ssw_backward_points: row b of both gradients is multiplied by pair_w[b] + total_w[0] (NULL terms count as 0, both
+ * NULL = 1); every gradient element is summed over the slices in a fixed order. */
+SHW_API int shw_ssw_backward_points_f64(const double* xs, const double* xt, const double* dirs, const double* coef_s,
+                                        const double* coef_t, int pairs, int n, int m, int slices, long u_pair_stride,
+                                        double scale, const double* pair_w, const double* total_w, double* grad_xs,
+                                        double* grad_xt, void* stream);
+
+/* Replaces: torch.mean(w1) (:286) and the `w1 += mean(...)` loop over the batch (_fast.py:291-293) in double, as
+ * shw_ssw_reduce: pair_loss (pairs), total (2, may be NULL) = {sum_b pair_loss[b], that / pairs}. */
+SHW_API int shw_ssw_reduce_f64(const double* slice_cost, int pairs, int slices, double scale, double* pair_loss,
+                               double* total, void* stream);
+
+/* Replaces: binary_search_circle (:117-207) and emd1D_circle (:210-247) on double rows of circle coordinates, equal
+ * sizes, no weights; `method` as in shw_circle_ot.  SHW_CIRCLE_BISECTION at p == 1 is the true circular W_1, for equal
+ * sizes and uniform weights again min_k c(k).
+ *   u, v (rows, n); cost (rows) out; aux (rows) int32 out, may be NULL: k* or the median level;
+ *   grad_u, grad_v (rows*n) out, both NULL for a value-only call. */
+SHW_API int shw_circle_ot_f64(const double* u, const double* v, int rows, int n, int m, double p, int method,
+                              double* cost, int32_t* aux, double* grad_u, double* grad_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Euclidean sliced-Wasserstein (the notebooks' SWD baseline).

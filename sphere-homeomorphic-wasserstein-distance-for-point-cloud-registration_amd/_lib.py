@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SHW_LIB_PATH") or os.path.join(_HERE, "libshw_hip.so")   # override: kernel A/B builds
 CSRC = os.path.join(_HERE, "csrc")
 
-_c_f32p = ctypes.c_void_p
+_c_f32p = ctypes.c_void_p     # device pointers of either precision travel as void*
 ABI_VERSION = 3           # include/shw.h SHW_ABI_VERSION
 CIRCLE_AS_SLICED, CIRCLE_BISECTION, CIRCLE_LEVEL_MEDIAN = 0, 1, 2      # include/shw.h SHW_CIRCLE_*
 _SIGNATURES = {
@@ -39,6 +39,20 @@ _SIGNATURES = {
     "shw_circle_ot": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _c_f32p, _c_f32p, _c_f32p,
                                      _c_f32p, ctypes.c_void_p]),
+    # float64 path (csrc/shw_ssw_f64.hip): equal sizes, uniform weights
+    "shw_max_points_f64": (ctypes.c_int, []),
+    "shw_stiefel_frames_f64": (ctypes.c_int, [_c_f32p, ctypes.c_long, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_forward_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_long, ctypes.c_double, _c_f32p, ctypes.c_void_p,
+                                           _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_backward_points_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                                   ctypes.c_double, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                   ctypes.c_void_p]),
+    "shw_ssw_reduce_f64": (ctypes.c_int, [_c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_f32p, _c_f32p,
+                                          ctypes.c_void_p]),
+    "shw_circle_ot_f64": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_int, _c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                        ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,

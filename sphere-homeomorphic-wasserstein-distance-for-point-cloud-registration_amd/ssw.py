@@ -9,15 +9,63 @@ max_spherical_sliced_w_fast.py (batched):
 
 PyTorch is plumbing here (device memory, streams, autograd bookkeeping); every number is produced by
 the hand-written gfx950 kernels.  CPU tensors are rejected: there is no fallback path.
+
+Precision follows the input, as in the reference (`dtype = u_values.dtype`, :153-160): float32 everywhere, and
+float64 for equal cloud sizes with uniform weights (any p >= 1, loss and gradients, sliced and circle level;
+kernels of csrc/shw_ssw_f64.hip, up to `max_points_f64()` points per cloud).  Clouds and directions share one dtype.
+float64 is OPT-IN: until `enable_float64()` is called (or the process starts with SHW_FLOAT64=1) double tensors raise
+TypeError as they always did, so that a caller who passes double by accident is told instead of paying ~9x.
 """
 from __future__ import annotations
 
+import os
 import threading
 from collections import OrderedDict
 
 import torch
 
 from . import _lib
+
+
+_FLOATS = (torch.float32, torch.float64)
+_float64_on = os.environ.get("SHW_FLOAT64", "0") == "1"
+
+
+def enable_float64(on=True) -> bool:
+    """Accept float64 clouds, directions and coordinate rows in the loss functions of this module (equal sizes, uniform
+    weights; see the module docstring).  Off by default: double input then raises TypeError, the behaviour before the
+    float64 kernels existed.  Process-wide; returns the previous setting so that a caller can restore it."""
+    global _float64_on
+    previous, _float64_on = _float64_on, bool(on)
+    return previous
+
+
+def float64_enabled() -> bool:
+    return _float64_on
+
+
+def _check_dtype(name, t):
+    if t.dtype == torch.float32 or (t.dtype == torch.float64 and _float64_on):
+        return
+    if t.dtype == torch.float64:
+        raise TypeError(f"{name} must be float32, got torch.float64: the float64 kernels are opt-in, call "
+                        "enable_float64() (or set SHW_FLOAT64=1) to use them")
+    raise TypeError(f"{name} must be float32 or float64, got {t.dtype}")
+
+
+def max_points_f64() -> int:
+    """Largest point count per cloud of the float64 path (`shw_max_points_f64`)."""
+    return int(_lib.load().shw_max_points_f64())
+
+
+def _check_f64_shape(n, m, weighted):
+    """The float64 kernels cover the reference's own call shape only; everything else says so instead of failing in HIP."""
+    if weighted or n != m:
+        raise ValueError("float64 input is supported for equal cloud sizes with uniform weights only (got "
+                         f"n = {n}, m = {m}{', weights' if weighted else ''}); weighted and unequal-size clouds are float32")
+    limit = max_points_f64()
+    if n > limit:
+        raise ValueError(f"float64 input is supported up to {limit} points per cloud, got {n}")
 
 
 def _stream_ptr(device) -> int:
@@ -29,18 +77,18 @@ def _check_cloud(name, t):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
         raise RuntimeError(f"{name} is on {t.device}: the MI355X HIP path needs device tensors (no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    _check_dtype(name, t)
     if t.shape[-1] != 3:
         raise ValueError(f"{name} must have 3 coordinates per point, got shape {tuple(t.shape)}")
 
 
-def draw_directions(num_projections, device, batch=None, d=3):
+def draw_directions(num_projections, device, batch=None, d=3, dtype=None):
     """Uniform samples on the Stiefel manifold V_{d,2} from the GLOBAL torch generator, consumed exactly
     like the reference (randn of (L,d,2) resp. (B,L,d,2) on `device`, then reduced QR; :307-308,
-    _fast.py:317-318)."""
+    _fast.py:317-318).  `dtype` None: the default dtype, as the reference's `torch.randn`; torch.float64 consumes the
+    generator as the reference does when the default dtype is float64."""
     shape = (num_projections, d, 2) if batch is None else (batch, num_projections, d, 2)
-    Z = torch.randn(shape, device=device)
+    Z = torch.randn(shape, device=device, dtype=dtype)
     return stiefel_frames(Z)
 
 
@@ -49,17 +97,18 @@ def stiefel_frames(Z):
     kernel `shw_stiefel_frames` (LAPACK's Householder steps and sign convention, one thread per matrix):
     torch.linalg.qr itself takes ~0.94 s for the 32 768 frames of config 3 on MI355X, and differs from the CPU
     LAPACK result by up to 6e-6; the kernel takes microseconds and agrees with LAPACK to fp32 rounding.  CPU
-    tensors (tests of the generator stream) go through torch.linalg.qr."""
+    tensors (tests of the generator stream) go through torch.linalg.qr.  float64 input runs the double form of the
+    kernel (`shw_stiefel_frames_f64`) and agrees with LAPACK to double rounding."""
     if not Z.is_cuda:
         return torch.linalg.qr(Z)[0]
-    if Z.dtype != torch.float32 or tuple(Z.shape[-2:]) != (3, 2):
-        raise TypeError("stiefel_frames expects float32 (..., 3, 2)")
+    if Z.dtype not in _FLOATS or tuple(Z.shape[-2:]) != (3, 2):
+        raise TypeError("stiefel_frames expects float32 or float64 (..., 3, 2)")
     lib = _lib.load()
     Zc = Z.contiguous()
     U = torch.empty_like(Zc)
+    name = "shw_stiefel_frames" if Z.dtype == torch.float32 else "shw_stiefel_frames_f64"
     with torch.cuda.device(Z.device):
-        _lib.check(lib.shw_stiefel_frames(Zc.data_ptr(), Zc.numel() // 6, U.data_ptr(), _stream_ptr(Z.device)),
-                   "shw_stiefel_frames")
+        _lib.check(getattr(lib, name)(Zc.data_ptr(), Zc.numel() // 6, U.data_ptr(), _stream_ptr(Z.device)), name)
     return U
 
 
@@ -67,7 +116,7 @@ class SSWWorkspace:
     """Persistent device buffers of one problem shape (B, n, m, L): the per-slice costs and shifts / cuts and --
     for training -- the two coefficient scratch rows that the slice kernel writes and the point-gradient kernel
     streams (2 x 268 MB at config 3).  Instances are leased from a small pool keyed by (device, stream,
-    shape) and come back when the evaluation that used them is over: at once for a loss-only call, and when the
+    shape, dtype) and come back when the evaluation that used them is over: at once for a loss-only call, and when the
     autograd node of a training call dies (after its backward, or when its graph is dropped) -- see `_Lease`.
     A phi-max inner loop (max_iter + 1 evaluations of one shape per step, _fast.py:359-377) thus alternates
     between two sets of buffers instead of asking the allocator for five tensors per evaluation, and nothing is
@@ -87,18 +136,19 @@ class SSWWorkspace:
     MAX_IDLE_BYTES = 4 << 30
 
     def __init__(self, key):
-        dev, _stream, B, n, m, L, with_coef = key
+        dev, _stream, B, n, m, L, dtype, with_coef = key
         self.key = key
         self.pooled = True
-        self.slice_cost = torch.empty(B * L, dtype=torch.float32, device=dev)
+        word = 4 if dtype == torch.float32 else 8
+        self.slice_cost = torch.empty(B * L, dtype=dtype, device=dev)
         self.slice_aux = torch.empty(B * L, dtype=torch.int32, device=dev)     # shift k* / median level / cut bits
-        self.coef_s = torch.empty(B * L * n, dtype=torch.float32, device=dev) if with_coef else None
-        self.coef_t = torch.empty(B * L * m, dtype=torch.float32, device=dev) if with_coef else None
-        self.nbytes = 8 * B * L + (4 * B * L * (n + m) if with_coef else 0)
+        self.coef_s = torch.empty(B * L * n, dtype=dtype, device=dev) if with_coef else None
+        self.coef_t = torch.empty(B * L * m, dtype=dtype, device=dev) if with_coef else None
+        self.nbytes = (word + 4) * B * L + (word * B * L * (n + m) if with_coef else 0)
 
     @classmethod
-    def lease(cls, dev, B, n, m, L, with_coef):
-        key = (torch.device(dev), _stream_ptr(dev), B, n, m, L, bool(with_coef))
+    def lease(cls, dev, B, n, m, L, with_coef, dtype=torch.float32):
+        key = (torch.device(dev), _stream_ptr(dev), B, n, m, L, dtype, bool(with_coef))
         if torch.cuda.is_current_stream_capturing():
             ws = cls(key)
             ws.pooled = False
@@ -171,15 +221,22 @@ class _PairLosses(torch.autograd.Function):
         dev = Xs.device
         Xs_c, Xt_c, Us_c = Xs.contiguous(), Xt.contiguous(), Us.contiguous()
         stride = 0 if shared_dirs else L * 6
-        ws = SSWWorkspace.lease(dev, B, n, m, L, need_grad)
-        out = torch.empty(B + 2, dtype=torch.float32, device=dev)        # [pair_loss (B) | total (2)]
+        dtype = Xs.dtype
+        f64 = dtype == torch.float64
+        ws = SSWWorkspace.lease(dev, B, n, m, L, need_grad, dtype)
+        out = torch.empty(B + 2, dtype=dtype, device=dev)                # [pair_loss (B) | total (2)]
         stream = _stream_ptr(dev)
         weighted = wu is not None or wv is not None
         general = weighted or (float(p) != 1.0 and n != m)      # p == 1 with uniform weights: level-median kernel
         cs = ws.coef_s.data_ptr() if need_grad else None
         ct = ws.coef_t.data_ptr() if need_grad else None
         with torch.cuda.device(dev):
-            if general:
+            if f64:
+                # equal sizes, uniform weights (checked by the caller): one entry for loss and training form
+                _lib.check(lib.shw_ssw_forward_f64(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), B, n, m, L,
+                                                   stride, float(p), ws.slice_cost.data_ptr(),
+                                                   ws.slice_aux.data_ptr(), cs, ct, stream), "shw_ssw_forward_f64")
+            elif general:
                 # n != m and / or weights: the reference's bisection over the cut, followed step for step
 
                 def wargs(w, cnt):
@@ -201,8 +258,12 @@ class _PairLosses(torch.autograd.Function):
                 _lib.check(lib.shw_ssw_forward(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), B, n, m, L, stride,
                                                float(p), ws.slice_cost.data_ptr(), ws.slice_aux.data_ptr(), stream),
                            "shw_ssw_forward")
-            _lib.check(lib.shw_ssw_reduce(ws.slice_cost.data_ptr(), B, L, 1.0 / L, out.data_ptr(),
-                                          out.data_ptr() + 4 * B, stream), "shw_ssw_reduce")
+            if f64:
+                _lib.check(lib.shw_ssw_reduce_f64(ws.slice_cost.data_ptr(), B, L, 1.0 / L, out.data_ptr(),
+                                                  out.data_ptr() + 8 * B, stream), "shw_ssw_reduce_f64")
+            else:
+                _lib.check(lib.shw_ssw_reduce(ws.slice_cost.data_ptr(), B, L, 1.0 / L, out.data_ptr(),
+                                              out.data_ptr() + 4 * B, stream), "shw_ssw_reduce")
         cost2d = shift2d = None
         if want_slices:
             cost2d = ws.slice_cost.view(B, L).clone()
@@ -231,21 +292,23 @@ class _PairLosses(torch.autograd.Function):
         if g_pair is None and g_total is None and g_first is None:
             return (None,) * 9
         # the upstream gradients go to the kernel as they are: row b is scaled by g_pair[b] + g_total[0] there
-        gp = g_pair.to(torch.float32).contiguous() if g_pair is not None else None
+        dtype = Xs_c.dtype
+        gp = g_pair.to(dtype).contiguous() if g_pair is not None else None
         if g_first is not None:                     # gradient of the 0-dim first-pair output: belongs to row 0
             if gp is None and B == 1:
-                gp = g_first.to(torch.float32).reshape(1)
+                gp = g_first.to(dtype).reshape(1)
             else:
-                gp = gp.clone() if gp is not None else torch.zeros(B, dtype=torch.float32, device=dev)
-                gp[0] += g_first.to(torch.float32)
-        gt = g_total.to(torch.float32).contiguous() if g_total is not None else None
+                gp = gp.clone() if gp is not None else torch.zeros(B, dtype=dtype, device=dev)
+                gp[0] += g_first.to(dtype)
+        gt = g_total.to(dtype).contiguous() if g_total is not None else None
+        entry = lib.shw_ssw_backward_points if dtype == torch.float32 else lib.shw_ssw_backward_points_f64
         with torch.cuda.device(dev):
-            _lib.check(lib.shw_ssw_backward_points(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
-                                                   ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
-                                                   1.0 / L, gp.data_ptr() if gp is not None else None,
-                                                   gt.data_ptr() if gt is not None else None, gxs.data_ptr(),
-                                                   gxt.data_ptr(), _stream_ptr(dev)),
-                       "shw_ssw_backward_points")
+            _lib.check(entry(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
+                             ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
+                             1.0 / L, gp.data_ptr() if gp is not None else None,
+                             gt.data_ptr() if gt is not None else None, gxs.data_ptr(),
+                             gxt.data_ptr(), _stream_ptr(dev)),
+                       "shw_ssw_backward_points" if dtype == torch.float32 else "shw_ssw_backward_points_f64")
         return gxs, gxt, None, None, None, None, None, None, None
 
 
@@ -266,10 +329,13 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     Returns (B,) per-pair losses = mean over slices of W_p^p on the slice circle
     [optionally also the (B,L) per-slice costs and optimal shifts; or, with return_total, the shape-[1] sum over
     pairs that the reduction kernel produces in the same launch (the batched reference value, _fast.py:291-293)].
-    Scratch (per-slice arrays, gradient coefficients) lives in a pooled SSWWorkspace; results are fresh tensors."""
+    Scratch (per-slice arrays, gradient coefficients) lives in a pooled SSWWorkspace; results are fresh tensors.
+    Losses, per-slice costs and gradients have the input's dtype; float64 needs n == m and no weights."""
     _check_cloud("Xs", Xs)
     _check_cloud("Xt", Xt)
     _check_cloud_dirs(Us)
+    if not (Xs.dtype == Xt.dtype == Us.dtype):
+        raise TypeError(f"Xs, Xt and Us must share one dtype, got {Xs.dtype}, {Xt.dtype}, {Us.dtype}")
     if Xs.dim() != 3 or Xt.dim() != 3 or Xs.shape[0] != Xt.shape[0]:
         raise ValueError("Xs and Xt must be (B,n,3) and (B,m,3) with the same B")
     shared = Us.dim() == 3
@@ -279,6 +345,8 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
         raise ValueError("p must be >= 1")
     if Us.shape[-3] < 1 or Xs.shape[1] < 1 or Xt.shape[1] < 1:
         raise ValueError("need at least one slice and one point per cloud")
+    if Xs.dtype == torch.float64:
+        _check_f64_shape(Xs.shape[1], Xt.shape[1], u_weights is not None or v_weights is not None)
     wu = _check_weights("u_weights", u_weights, Xs.shape[1], Xs.shape[0], Xs.device)
     wv = _check_weights("v_weights", v_weights, Xt.shape[1], Xs.shape[0], Xs.device)
     # evaluation under torch.no_grad() on inputs that still carry requires_grad must not run the
@@ -296,8 +364,9 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
 
 
 def _check_cloud_dirs(Us):
-    if not isinstance(Us, torch.Tensor) or not Us.is_cuda or Us.dtype != torch.float32:
-        raise TypeError("Us must be a float32 device tensor")
+    if not isinstance(Us, torch.Tensor) or not Us.is_cuda:
+        raise TypeError("Us must be a float32 or float64 device tensor")
+    _check_dtype("Us", Us)
     if Us.dim() not in (3, 4) or tuple(Us.shape[-2:]) != (3, 2):
         raise ValueError(f"Us must be (L,3,2) or (B,L,3,2), got {tuple(Us.shape)}")
 
@@ -306,7 +375,10 @@ def sliced_cost(Xs, Xt, Us, p=2, u_weights=None, v_weights=None):
     """Reference `sliced_cost`.  Per pair -- Xs (n,3), Xt (m,3), Us (L,3,2) -> 0-dim tensor, the mean
     over slices (:286).  Batched -- Xs (B,n,3), Xt (B,m,3), Us (B,L,3,2) -> shape-[1] tensor, the SUM
     over pairs of the per-pair means (_fast.py:291-293).  Batched p == 1, which raises in the
-    reference, is evaluated pair-wise here (documented extension)."""
+    reference, is evaluated pair-wise here (documented extension).
+    The result has the input's dtype.  For the batched total this differs from the reference on double input: it
+    accumulates in `torch.zeros((1))` (_fast.py:291), which has the DEFAULT dtype, and so returns float32 for double
+    clouds unless the default dtype is float64; here double clouds give a double total."""
     if Xs.dim() == 2:
         return ssw_pair_losses(Xs.unsqueeze(0), Xt.unsqueeze(0), Us, p, u_weights=u_weights, v_weights=v_weights,
                                return_first=True)
@@ -316,13 +388,13 @@ def sliced_cost(Xs, Xt, Us, p=2, u_weights=None, v_weights=None):
 
 def sliced_wasserstein_sphere(Xs, Xt, num_projections, device, u_weights=None, v_weights=None, p=2):
     """Reference signature (:289).  Xs (n,3), Xt (m,3) on `device` -> 0-dim tensor."""
-    U = draw_directions(num_projections, device, d=Xs.shape[1])
+    U = draw_directions(num_projections, device, d=Xs.shape[1], dtype=Xs.dtype)
     return sliced_cost(Xs, Xt, U, p=p, u_weights=u_weights, v_weights=v_weights)
 
 
 def sliced_wasserstein_sphere_fast(Xs, Xt, num_projections, device, u_weights=None, v_weights=None, p=2):
     """Reference batched signature (_fast.py:298).  Xs (B,n,3), Xt (B,m,3) -> shape-[1] tensor."""
-    U = draw_directions(num_projections, device, batch=Xs.shape[0], d=Xs.shape[2])
+    U = draw_directions(num_projections, device, batch=Xs.shape[0], d=Xs.shape[2], dtype=Xs.dtype)
     return sliced_cost(Xs, Xt, U, p=p, u_weights=u_weights, v_weights=v_weights)
 
 
@@ -340,9 +412,18 @@ class _CircleOT(torch.autograd.Function):
         m = v.shape[1]
         dev = u.device
         uc, vc = u.contiguous(), v.contiguous()
-        cost = torch.empty(rows, dtype=torch.float32, device=dev)
-        gu = torch.empty(rows, n, dtype=torch.float32, device=dev) if need_grad else None
-        gv = torch.empty(rows, m, dtype=torch.float32, device=dev) if need_grad else None
+        cost = torch.empty(rows, dtype=u.dtype, device=dev)
+        gu = torch.empty(rows, n, dtype=u.dtype, device=dev) if need_grad else None
+        gv = torch.empty(rows, m, dtype=u.dtype, device=dev) if need_grad else None
+        if u.dtype == torch.float64:                # equal sizes, no weights (checked by the caller)
+            with torch.cuda.device(dev):
+                _lib.check(lib.shw_circle_ot_f64(uc.data_ptr(), vc.data_ptr(), rows, n, m, float(p), int(method),
+                                                 cost.data_ptr(), None, gu.data_ptr() if need_grad else None,
+                                                 gv.data_ptr() if need_grad else None, _stream_ptr(dev)),
+                           "shw_circle_ot_f64")
+            if need_grad:
+                ctx.save_for_backward(gu, gv)
+            return cost
 
         def wargs(w, cnt):
             if w is None:
@@ -361,13 +442,14 @@ class _CircleOT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         gu, gv = ctx.saved_tensors
-        w = g.to(torch.float32).unsqueeze(1)
+        w = g.to(gu.dtype).unsqueeze(1)
         return gu * w, gv * w, None, None, None, None, None
 
 
 def _check_rows(name, t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise TypeError(f"{name} must be a float32 device tensor (no CPU fallback)")
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError(f"{name} must be a float32 or float64 device tensor (no CPU fallback)")
+    _check_dtype(name, t)
     if t.dim() not in (1, 2):
         raise ValueError(f"{name} must be (n,) or (rows, n) circle coordinates")
     return t.unsqueeze(0) if t.dim() == 1 else t
@@ -377,8 +459,14 @@ def _circle_ot(u_values, v_values, u_weights, v_weights, p, method):
     u, v = _check_rows("u_values", u_values), _check_rows("v_values", v_values)
     if u.shape[0] != v.shape[0]:
         raise ValueError("u_values and v_values need the same number of rows")
+    if u.dtype != v.dtype:
+        raise TypeError(f"u_values and v_values must share one dtype, got {u.dtype} and {v.dtype}")
     if not (float(p) >= 1.0):
         raise ValueError("p must be >= 1")
+    if u.dtype == torch.float64:
+        if u.shape[1] < 1 or v.shape[1] < 1:
+            raise ValueError("need at least one coordinate per row")
+        _check_f64_shape(u.shape[1], v.shape[1], u_weights is not None or v_weights is not None)
     wu = _check_weights("u_weights", u_weights, u.shape[1], u.shape[0], u.device)
     wv = _check_weights("v_weights", v_weights, v.shape[1], u.shape[0], u.device)
     need_grad = torch.is_grad_enabled() and (u.requires_grad or v.requires_grad)
