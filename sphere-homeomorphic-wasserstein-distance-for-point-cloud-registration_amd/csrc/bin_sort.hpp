@@ -5,24 +5,34 @@
 // 66 stages x 32 keys = 2112 slow-rate instructions + 672 crossbar moves per 2048-key sort, and two of them are
 // 70 % of the loss kernel.  Circle coordinates are numbers in [0, 1] -- a key's value says where it belongs:
 //
-//   1. histogram   b = min(floor(key * NB), NB-1);  ds_add(cnt[b], 1)                     (NB = 32*EPT bins: 2 keys per
+//   1. histogram   off = 4 * bin(key), a monotone map of the key onto the counters that is already the counter's byte
+//                  offset (binsort_off: one FMA and one AND);  ds_add(cnt + off, 4)       (NB = 32*EPT bins: 2 keys per
 //                                                                                          bin on average)
-//   2. scan        exclusive prefix sum over the NB counters (16 per lane in-lane, then a wave scan); the largest
-//                  counter g is the longest run of keys that share a bin
-//   3. scatter     b recomputed; buf[ds_add_rtn(start[b], 1)] = key   (keys are now ordered by bin; inside a bin in
-//                  arrival order).  No per-key word lives from 1 to 3: the one-wave loss kernel sorts the target while
-//                  it holds the sorted source in registers, and a rank per key beside both made it spill.
+//   2. scan        exclusive prefix sum over the NB counters (16 per lane in-lane, then a wave scan).  The counters count
+//                  BYTES (4 per key), so the scan leaves the byte position of every bin's first key; the largest
+//                  counter / 4 = g is the longest run of keys that share a bin
+//   3. scatter     buf[perm(ds_add_rtn(cnt + off, 4))] = key   (keys are now ordered by bin; inside a bin in arrival
+//                  order).  `off` is NOT recomputed: the compiler keeps the EPT offsets of step 1 in registers across the
+//                  scan (registers, not instructions: the loss kernel stays spill-free).  No other per-key word lives
+//                  from 1 to 3: the one-wave loss kernel sorts the target while it holds the sorted source in registers,
+//                  and a rank per key beside both made it spill.
 //   4. read back   32 consecutive positions per lane (sorted position of x[r] in lane `lane` is lane*EPT + r, the
 //                  layout wave_sort leaves)
 //   5. fix-up      g phases of odd-even transposition (in-lane compare-exchanges + one exchange across each lane
 //                  boundary per odd phase): every run of equal-bin keys is at most g long and no key has to leave its
 //                  run, so g phases put every run -- hence the whole array -- into exact ascending order.
 //
-// ~8 VALU + 3 LDS instructions per key for steps 1-4 and 33 slow-rate instructions per lane per phase: with g ~ 8
-// (uniformly spread coordinates) a quarter of the network's VALU work and an eighth of its crossbar traffic.
+// Per key, steps 1-4: 2 full-rate VALU (FMA, AND) + ds_add in the histogram, 3 full-rate VALU (shift, AND, XOR: the
+// staging address from the byte position) + ds_add_rtn + ds_write in the placement, a quarter of a ds_read_b128; then 33
+// slow-rate instructions per lane per phase: with g ~ 8 (uniformly spread coordinates) a quarter of the network's VALU
+// work and an eighth of its crossbar traffic.
 // The result is the exact ascending order of the fp32 keys whatever order the atomics were served in.
 // Data with long runs (clustered clouds, duplicates, an all-zero cloud: g > SHW_BINSORT_MAX_RUN) is detected
 // after step 2 -- before any key has moved -- and the caller sorts it with the network instead (wave-uniform branch).
+// So are rows of caller-supplied coordinates with a value outside [0, 1] (binsort_keys_fit): the map does not saturate.
+// The above is the form of the FULL classes (n == 64*EPT).  Classes with pads keep the earlier form -- bin =
+// min(floor(key * NB), NB-1) by a saturating v_cvt, counters in keys, pads steered by selects -- because the new one
+// made their kernels slower (see below, "the classes with pads").
 //
 // LDS per wave: NB counters (128*EPT bytes) + a 64*EPT-float staging buffer (256*EPT bytes).  LDS operations of one
 // wave execute in order and nothing here is shared with another wave: no barrier.
@@ -43,11 +53,29 @@
 #define SHW_BINSORT_MAX_RUN 40
 #endif
 // the cooperative sorts (several waves per slice) finish a run that straddles two waves inside a 64-key window: < 32
+// 1: the counter offsets of the histogram pass are held in registers for the placement pass (an empty asm makes them
+// opaque: left alone the compiler recomputes the FMA and the AND per key there, 2 x 64 more VALU instructions per slice
+// and 34 fewer VGPRs); 0: the compiler chooses
+#ifndef SHW_BINSORT_KEEP_OFF
+#define SHW_BINSORT_KEEP_OFF 1
+#endif
+#if SHW_BINSORT_KEEP_OFF
+#define BINSORT_PIN_OFF(x) asm volatile("" : "+v"(x))
+#else
+#define BINSORT_PIN_OFF(x) ((void)0)
+#endif
 #ifndef SHW_COOP_MAX_RUN
 #define SHW_COOP_MAX_RUN 24
 #endif
 
 namespace shw {
+
+// a counter by its 32-bit LDS address (kept per key from the histogram pass to the placement pass)
+typedef __attribute__((address_space(3))) unsigned lds_u32;
+__device__ __forceinline__ unsigned lds_address(const void* p) {
+  return (unsigned)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+__device__ __forceinline__ lds_u32* lds_counter(unsigned address) { return (lds_u32*)(uintptr_t)address; }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -68,6 +96,11 @@ __device__ __forceinline__ unsigned binsort_addr(unsigned pos) {
   // bit 6 of pos is bit k of the row number in every size class: (pos >> 2) puts it on the chunk-index bits
   return (pos << 2) ^ ((pos >> 2) & (unsigned)((EPT / 4 - 1) << 4));
 }
+// the same address from the BYTE position p4 = 4 pos, which is what the scanned counters hand out: no shift to bytes
+template <int EPT>
+__device__ __forceinline__ unsigned binsort_addr4(unsigned p4) {
+  return p4 ^ ((p4 >> 4) & (unsigned)((EPT / 4 - 1) << 4));
+}
 
 // inclusive prefix sum over the lanes of a wave (row_shr DPP steps inside rows of 16, then the two row broadcasts)
 __device__ __forceinline__ int wave_inclusive_scan_dpp(int v) {
@@ -82,6 +115,162 @@ __device__ __forceinline__ int wave_inclusive_scan_dpp(int v) {
   return v;
 }
 
+// Byte offset of a key's counter: 4 * bin, bin in [0, NB), monotone non-decreasing in the key over [0, 1].
+//     off = bits(fma(key, 4 NB - 1, 2^23)) & (next_pow2(4 NB) - 4)
+// For key in [0, 1] the sum lies in [2^23, 2^23 + 4 NB - 1]: there an fp32 ulp is 1, so the rounding of the FMA leaves
+// round(key (4 NB - 1)) in the low mantissa bits (rounding is monotone); the mask drops the exponent and the two low
+// bits (monotone again), leaving a multiple of 4 that is at most 4 NB - 4 (also where 4 NB is no power of two: 768
+// bins, mask 4092, value at most 3071 -- tests/test_bin_map_cpu.py -- though no such class uses it today).  One FMA + one AND, both full rate, against v_mul + v_cvt_u32 +
+// v_min_u32 (quarter rate) + a shift to bytes for min(floor(key NB), NB - 1).  Any monotone map sorts exactly: the
+// fix-up phases order every equal-bin run, and g is measured on the bins actually used.
+//   * -0 and denormals -> bin 0;  1 and the float above it -> bin NB - 1  (round((1 + 2^-23)(4 NB - 1)) = 4 NB - 1);
+//   * NaN -> the low bits of a NaN: 0 for the canonical quiet NaN, always a multiple of 4 below 4 NB (full classes are
+//     powers of two), i.e. inside the counters (in bounds; NaN input has no defined order anyway);
+//   * the map does NOT saturate: 1.5 -> bin (NB - 1) / 2, -0.25 -> NB / 2, +inf -> 0.  Keys outside [0, 1] must not come
+//     here.  Projected coordinates never are: circle_coord (ssw_common.hpp) returns (ang + pi) (1 / 2 pi) with ang in
+//     [-fl(pi), fl(pi)], so the largest value is fl(2 fl(pi) fl(1 / 2 pi)) = 1.0 exactly and the smallest +0.  Pads (+inf)
+//     do not exist in the full classes, the only ones that use this map.  Rows of caller-supplied coordinates
+//     (shw_circle_ot) are tested by binsort_keys_fit and take the network when a value is out of range (wave_sort_binned).
+template <int NB>
+__device__ __forceinline__ unsigned binsort_off(float key) {
+  constexpr unsigned kMask = (unsigned)next_pow2_c(4 * NB) - 4u;
+  return (unsigned)as_i(__builtin_fmaf(key, (float)(4 * NB - 1), 8388608.f)) & kMask;
+}
+
+// Rows of circle coordinates come from the caller (coordinate-row mode), who may pass values outside [0, 1]; the exact
+// order of such a row is still owed.  Wave-uniform: true when every key of the wave lies in [0, 1] (NaN: false).
+// Only evaluated in coordinate-row mode -- the projection path pays one scalar branch per sort for it.
+template <int EPT>
+__device__ __forceinline__ bool binsort_keys_fit(const float (&key)[EPT]) {
+  bool bad = false;
+#pragma unroll
+  for (int r = 0; r < EPT; ++r) bad |= !(key[r] >= 0.f && key[r] <= 1.f);
+  return __ballot(bad) == 0ull;
+}
+
+// one compare-exchange between the last key of every lane and the first key of the next lane
+template <int EPT>
+__device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
+  const float nxt = as_f(__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, as_i(x[0])));
+  const float prv = as_f(__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, as_i(x[EPT - 1])));
+  const float hi = __builtin_fminf(x[EPT - 1], lane < 63 ? nxt : __builtin_inff());
+  const float lo = __builtin_fmaxf(x[0], lane > 0 ? prv : -__builtin_inff());
+  x[EPT - 1] = hi;
+  x[0] = lo;
+}
+
+// Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition
+template <int EPT>
+__device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int lane, int g, float* buf) {
+  char* bytes = reinterpret_cast<char*>(buf);
+#pragma unroll
+  for (int j = 0; j < EPT / 4; ++j) {
+    const unsigned pos0 = (unsigned)lane * EPT + 4u * j;          // logical chunk j of row `lane`
+    const f32x4 v = *reinterpret_cast<const f32x4*>(bytes + binsort_addr<EPT>(pos0));
+    key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
+  }
+  // odd-even transposition, g phases (wave-uniform trip count)
+  for (int phase = 0; phase < g; phase += 2) {
+#pragma unroll
+    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
+    if (phase + 1 < g) {
+#pragma unroll
+      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
+      binsort_boundary<EPT>(key, lane);
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+// ---- the full classes (n == 64*EPT, no pads): byte-offset map, counters in bytes --------------------------------------
+// Steps 1-2.  Returns the longest equal-bin run g (wave-uniform); on return cnt[] holds the exclusive prefix sums (the
+// first sorted position of every bin, in bytes).  key[r] belongs to point r*64 + lane.  No rank is returned:
+// binsort_place_full takes the position from an atomic on the scanned starts.  slot[r] = LDS address of the counter of
+// key[r], kept for binsort_place_full.
+template <int EPT>
+__device__ __forceinline__ int binsort_histogram_full(const float (&key)[EPT], int lane, unsigned* cnt, unsigned (&slot)[EPT]) {
+  constexpr int NB = binsort_bins<EPT>();
+  constexpr int BPL = NB / 64;                          // bins per lane in the scan (EPT/2: 16 at EPT = 32)
+  static_assert(BPL >= 4 && BPL % 4 == 0, "bin sort needs >= 4 bins per lane");
+  // zero the counters: every ds_write_b128 covers 1 KB of consecutive addresses (conflict-free)
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j)
+    *reinterpret_cast<u32x4*>(cnt + j * 256 + lane * 4) = u32x4{0u, 0u, 0u, 0u};
+  __builtin_amdgcn_wave_barrier();
+  const unsigned cb = lds_address(cnt);                  // the counters by byte address
+  constexpr int CH = chunk_of(EPT);                      // rows per chunk (the placement's atomics in flight per lane)
+#pragma unroll
+  for (int r0 = 0; r0 < EPT; r0 += CH) {
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {                       // result unused: ds_add_u32, nothing to wait for
+      slot[r0 + j] = cb + binsort_off<NB>(key[r0 + j]);
+      BINSORT_PIN_OFF(slot[r0 + j]);
+      __hip_atomic_fetch_add(lds_counter(slot[r0 + j]), 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_amdgcn_wave_barrier();
+  // scan: lane owns bins [lane*BPL, (lane+1)*BPL)
+  unsigned c[BPL];
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + lane * BPL + j * 4);
+    c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
+  }
+  unsigned run = 0, total = 0;
+#pragma unroll
+  for (int j = 0; j < BPL; ++j) {
+    run = c[j] > run ? c[j] : run;
+    const unsigned t = c[j];
+    c[j] = total;                                        // exclusive inside the lane
+    total += t;
+  }
+  const int incl = wave_inclusive_scan_dpp((int)total);
+  const unsigned base = (unsigned)incl - total;
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j)
+    *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
+        u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
+  __builtin_amdgcn_wave_barrier();
+  // wave maximum of the run lengths (counted in bytes: four per key)
+  int g = (int)run;
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x111, 0xf, 0xf, false));
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x112, 0xf, 0xf, false));
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x114, 0xf, 0xf, false));
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x118, 0xf, 0xf, false));
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x142, 0xa, 0xf, false));
+  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x143, 0xc, 0xf, false));
+  return __builtin_amdgcn_readlane(g, 63) >> 2;
+}
+
+// Steps 3-5 of a full class (only after binsort_histogram_full returned g <= SHW_BINSORT_MAX_RUN).  The byte position of
+// a key is what ds_add_rtn(4) returns on its bin's scanned start (cnt[] holds the bin ends afterwards); inside a bin the
+// keys land in the order the atomics are served, which the fix-up phases make irrelevant.
+template <int EPT>
+__device__ __forceinline__ void binsort_place_full(float (&key)[EPT], const unsigned (&slot)[EPT], int lane, int g,
+                                                   float* buf) {
+  char* bytes = reinterpret_cast<char*>(buf);
+  constexpr int CH = chunk_of(EPT);
+#pragma unroll
+  for (int r0 = 0; r0 < EPT; r0 += CH) {
+    unsigned pos[CH];
+#pragma unroll
+    for (int j = 0; j < CH; ++j)
+      pos[j] = __hip_atomic_fetch_add(lds_counter(slot[r0 + j]), 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) *reinterpret_cast<float*>(bytes + binsort_addr4<EPT>(pos[j])) = key[r0 + j];
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __builtin_amdgcn_wave_barrier();
+  binsort_read_back_and_fix<EPT>(key, lane, g, buf);
+}
+
+// ---- the classes with pads (n < 64*EPT): the saturating map, counters in keys -----------------------------------------
+// Kept as they were.  With the byte-offset map, byte counters and unsigned point offsets together the two-wave loss kernel of
+// the partly filled classes lost on MI355X (N = 2000: 0.2823 -> 0.3037 ms per step, N = 1200: 0.1692 -> 0.1759, B = 64,
+// L = 512; registers 168 -> 116 at 32 keys per lane: the compiler no longer overlaps the chunks' loads), while every full
+// class gained (N = 2048: 0.2076 -> 0.1991, N = 1024: 0.1054 -> 0.1018).  The map below saturates, so these classes also
+// need no range test in coordinate-row mode.
 // bin of a key: v_cvt_u32_f32 saturates (NaN -> 0, +inf -> 0xffffffff), so the bin is always inside [0, NB).  The
 // histogram and the placement both compute it with this one function: a key lands in the bin it was counted in.
 template <int NB>
@@ -166,17 +355,6 @@ __device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], int la
   g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x142, 0xa, 0xf, false));
   g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x143, 0xc, 0xf, false));
   return __builtin_amdgcn_readlane(g, 63);
-}
-
-// one compare-exchange between the last key of every lane and the first key of the next lane
-template <int EPT>
-__device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
-  const float nxt = as_f(__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, as_i(x[0])));
-  const float prv = as_f(__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, as_i(x[EPT - 1])));
-  const float hi = __builtin_fminf(x[EPT - 1], lane < 63 ? nxt : __builtin_inff());
-  const float lo = __builtin_fmaxf(x[0], lane > 0 ? prv : -__builtin_inff());
-  x[EPT - 1] = hi;
-  x[0] = lo;
 }
 
 // Steps 3-5 (only after binsort_histogram returned g <= SHW_BINSORT_MAX_RUN).  The position of a live key is what
@@ -264,27 +442,34 @@ __device__ __forceinline__ void wave_sort_relayout(T (&key)[EPT], int lane, T ma
 }
 
 // Sort the 64*EPT keys of a wave ascending (pads = +inf behind the n live keys).  Falls back to the bitonic network
-// when the data has runs longer than SHW_BINSORT_MAX_RUN.  scratch: 32*EPT counters followed by 64*EPT floats.
+// when the data has runs longer than SHW_BINSORT_MAX_RUN, or -- full classes -- when `rows` (wave-uniform: the keys are
+// caller-supplied coordinates, not projections) and a key lies outside [0, 1], the domain of the byte-offset map.
+// scratch: binsort_bins<EPT>() counters with the 64*EPT floats of the staging buffer directly behind them (one block).
 // Returns the longest run of keys that share a bin (> SHW_BINSORT_MAX_RUN: the slice took the network).
 template <int EPT, bool FULL>
-__device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* counters, float* buf) {
-  unsigned* cnt = reinterpret_cast<unsigned*>(counters);
-  const int g = binsort_histogram<EPT, FULL>(key, lane, n, cnt);
-  if (g <= SHW_BINSORT_MAX_RUN) {
-    binsort_place<EPT, FULL>(key, lane, n, g, cnt, buf);
+__device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* scratch, bool rows) {
+  unsigned* cnt = reinterpret_cast<unsigned*>(scratch);
+  float* buf = scratch + binsort_bins<EPT>();
+  int g = SHW_BINSORT_MAX_RUN + 1;
+  if constexpr (FULL) {
+    unsigned slot[EPT];
+    if (!rows || binsort_keys_fit<EPT>(key)) g = binsort_histogram_full<EPT>(key, lane, cnt, slot);
+    if (g <= SHW_BINSORT_MAX_RUN) {
+      binsort_place_full<EPT>(key, slot, lane, g, buf);
+      return g;
+    }
   } else {
-#ifndef SHW_ABL_NO_FALLBACK
-    if constexpr (is_pow2(EPT)) wave_sort<EPT>(key, lane);
-    else wave_sort_relayout<EPT, float>(key, lane, __builtin_inff(), buf);
-#endif
+    g = binsort_histogram<EPT, FULL>(key, lane, n, cnt);
+    if (g <= SHW_BINSORT_MAX_RUN) {
+      binsort_place<EPT, FULL>(key, lane, n, g, cnt, buf);
+      return g;
+    }
   }
+#ifndef SHW_ABL_NO_FALLBACK
+  if constexpr (is_pow2(EPT)) wave_sort<EPT>(key, lane);
+  else wave_sort_relayout<EPT, float>(key, lane, __builtin_inff(), buf);
+#endif
   return g;
-}
-
-// counters and staging buffer contiguous: binsort_bins<EPT>() counters followed by 64*EPT floats
-template <int EPT, bool FULL>
-__device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* scratch) {
-  return wave_sort_binned<EPT, FULL>(key, lane, n, scratch, scratch + binsort_bins<EPT>());
 }
 
 }  // namespace shw

@@ -46,7 +46,9 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr bool BINS = forward_uses_bins(EPT);
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // (one wave per workgroup: a literal 0 makes the LDS addresses of the sort constants -- the counter of a key is then
+  //  ds_add(off) with no base to add)
+  const int wave = WAVES == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float* scratch = lds + wave * forward_lds_floats(EPT);
   float* vbuf = BINS ? scratch + SHW_BINSORT_NB_PER_EPT * EPT : scratch;       // the staging buffer of the sort becomes the target row
 
@@ -86,10 +88,10 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
     const float part = load_coords<EPT, FULL, false, kWave, false, (EPT == 32 && FULL) ? 16 : 8>(X, count, ln, U, key);
 #endif
 #ifdef SHW_DBG_RUNLEN          // developer build (tools/nonuniform_time.py): slice_shift reports the longest equal-bin run
-    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL>(key, ln, count, scratch));
+    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL>(key, ln, count, scratch, A.dirs == nullptr));
     else wave_sort<EPT>(key, ln);
 #else
-    if constexpr (BINS) wave_sort_binned<EPT, FULL>(key, ln, count, scratch);
+    if constexpr (BINS) wave_sort_binned<EPT, FULL>(key, ln, count, scratch, A.dirs == nullptr);
     else wave_sort<EPT>(key, ln);
 #endif
     if (which == 0) {

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(128, SHW_FWD2_MINW) void ssw_forward2_kernel(SswArg
   {
     const float* X = (wave ? A.xt : A.xs) + (long)b * n * A.pstride;
     const float part = load_coords<EPT, FULL, true>(X, n, lane, U, key);
-    wave_sort_binned<EPT, FULL>(key, lane, n, my_scr);
+    wave_sort_binned<EPT, FULL>(key, lane, n, my_scr, A.dirs == nullptr);
     const float total = wave_sum_uniform(part, lane);
     if (FULL || wave == 0) {                               // (partial sizes: the target goes out as extended rows below)
 #pragma unroll

@@ -130,7 +130,7 @@ ssw_level_median_merge_kernel(SswArgs A, int mg, int ng, float inv_lcm) {
           const bool live = key[r] != __builtin_inff();
           key[r] = live ? as_f((int)(((unsigned)as_i(key[r]) & ~1u) | (unsigned)wave)) : key[r];
         }
-        wave_sort_binned<EPT, false>(key, lane, count, lds + wave * (binsort_bins<EPT>() + CHUNK));
+        wave_sort_binned<EPT, false>(key, lane, count, lds + wave * (binsort_bins<EPT>() + CHUNK), A.dirs == nullptr);
 #pragma unroll
         for (int r = 0; r < EPT; ++r) pk[r] = (unsigned)as_i(key[r]);
         __syncthreads();                                    // both sorts done: their scratch becomes the exchange buffer

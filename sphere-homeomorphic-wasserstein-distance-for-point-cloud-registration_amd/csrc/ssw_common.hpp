@@ -91,6 +91,9 @@ __device__ __forceinline__ void load_frame(const float* dirs, long offset, float
 // <= 3e-8 in coordinate units = half an fp32 ulp of a coordinate in [0.5, 1)) and octant fix-ups that
 // follow the IEEE
 // signed-zero rules the reference relies on: a = b = +0 gives atan2(-0,-0) = -pi, i.e. coord 0.
+// Range: r ends in [0, fl(pi)], so ang lies in [-fl(pi), fl(pi)] and ang + fl(pi) in [+0, 2 fl(pi)] (exact); times
+// fl(1 / 2 pi) the largest value rounds to 1.0 exactly (2 fl(pi) fl(1 / 2 pi) = 1 - 1.3e-8, nearer to 1 than to the float
+// below it): every coordinate is in [0, 1], the domain of the bin map of bin_sort.hpp.
 // Domain note: |a|,|b| below 1e-37 (denormal-scale projections) are treated as if max(|a|,|b|) were
 // 1e-37, i.e. the angle of such a vector is not resolved; exact zeros are handled exactly.
 __device__ __forceinline__ float circle_coord(float a, float b) {
@@ -660,12 +663,14 @@ __device__ __forceinline__ float load_coords(const float* __restrict__ X, int co
   // training 0.62 -> 0.80 ms; folded it costs 2 + 1 VALU per point.  (The loss kernels spill less with the branch.)
   const bool rows = U[0] != U[0];
   constexpr bool kFold = FOLD && !FULL;
+  constexpr bool kScalarBase = FULL;               // how the point loads are addressed, see below
   if constexpr (!kFold) {
     if (rows) {
 #pragma unroll
       for (int r = 0; r < EPT; ++r) {
         const int i = r * NCOL + lane;
-        const float c = X[FULL ? i : min(i, count - 1)];
+        // (addressing: see the point loads below)
+        const float c = kScalarBase ? (X + r * NCOL)[(size_t)(unsigned)lane] : X[FULL ? i : min(i, count - 1)];
         const bool live = FULL || (i < live_count);
         acc += live ? c : 0.f;
         key[r] = live ? c : __builtin_inff();
@@ -696,12 +701,26 @@ __device__ __forceinline__ float load_coords(const float* __restrict__ X, int co
     // lane owns points r*NCOL + lane: when every point of the chunk's rows exists (uniform over the wave) the chunk is
     // the code of a full class -- no clamped addresses, no masks; only the one mixed chunk of a cloud pays for them
     const bool whole = FULL || (!is_pow2(EPT) && (r0 + CH) * NCOL <= (live_count < count ? live_count : count));   // (classes: bin_sort.hpp)
+    // Addresses of a full class: a wave-uniform 64-bit base (the cloud plus the row) and ONE unsigned 32-bit offset per
+    // lane, widened before the +1 / +2 so that these go into the load's immediate field and the three loads of a record
+    // still merge into a dwordx3.  A signed index costs an add, a sign extension and a 64-bit shift-add per record
+    // instead.  A cloud has at most 8192 points: 3 * 4 * 8192 bytes, far below 2^32.
+    // (The classes with pads keep the signed index, in the clamped path too: given unsigned offsets together with the
+    //  byte-offset bin map, the two-wave loss kernel lost 4..8 % at N = 1200 / 2000 -- see bin_sort.hpp; which of the two
+    //  cost it was not separated -- and the 8192-point training kernel began to spill, 0 -> 36 registers.)
     if (whole) {
+      const size_t o3 = (size_t)(3u * (unsigned)lane);
+      (void)o3;
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
-        const int i = (r0 + j) * NCOL + lane;
-        const int i3 = kFold ? i + ((i & wide) << 1) : 3 * i;
-        px[j] = X[i3]; py[j] = X[i3 + (kFold ? o1 : 1)]; pz[j] = X[i3 + (kFold ? o2 : 2)];
+        if constexpr (kFold || !kScalarBase) {
+          const int i = (r0 + j) * NCOL + lane;
+          const int i3 = kFold ? i + ((i & wide) << 1) : 3 * i;
+          px[j] = X[i3]; py[j] = X[i3 + (kFold ? o1 : 1)]; pz[j] = X[i3 + (kFold ? o2 : 2)];
+        } else {
+          const float* row = X + 3 * (r0 + j) * NCOL;
+          px[j] = row[o3]; py[j] = row[o3 + 1]; pz[j] = row[o3 + 2];
+        }
       }
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
