@@ -23,9 +23,13 @@
 //                  run, so g phases put every run -- hence the whole array -- into exact ascending order.
 //
 // Per key, steps 1-4: 2 full-rate VALU (FMA, AND) + ds_add in the histogram, 3 full-rate VALU (shift, AND, XOR: the
-// staging address from the byte position) + ds_add_rtn + ds_write in the placement, a quarter of a ds_read_b128; then 33
-// slow-rate instructions per lane per phase: with g ~ 8 (uniformly spread coordinates) a quarter of the network's VALU
-// work and an eighth of its crossbar traffic.
+// staging address from the byte position) + ds_add_rtn + ds_write in the placement, a quarter of a ds_read_b128; then, per
+// lane and per loop trip of two phases (31 in-lane compare-exchanges + the one across the lane boundary = 64 v_min /
+// v_max at the source level), as compiled for the headline kernel: up to round 6 130 slow-rate v_min / v_max, 66 of
+// them `v_max x, y, y` canonicalisations of the operands (see F32KeysRaw below; the "33 per phase" of earlier rounds was
+// the source-level count); since round 7, in the full classes, the 64 + 31 full-rate v_mov that rotate the loop's
+// registers (a loop of four phases compiles without them: profiles/r07_forward_summary.txt; not measured, not taken).
+// With g ~ 9 (uniformly spread coordinates) a quarter of the network's VALU work and an eighth of its crossbar traffic.
 // The result is the exact ascending order of the fp32 keys whatever order the atomics were served in.
 // Data with long runs (clustered clouds, duplicates, an all-zero cloud: g > SHW_BINSORT_MAX_RUN) is detected
 // after step 2 -- before any key has moved -- and the caller sorts it with the network instead (wave-uniform branch).
@@ -44,8 +48,9 @@
 #ifndef SHW_BINSORT_NB_PER_EPT
 #define SHW_BINSORT_NB_PER_EPT 32
 #endif
-// Longest equal-bin run the one-wave sorts fix up by odd-even phases (one phase ~ 33 quarter-rate instructions per lane,
-// ~60 ns) before they prefer the bitonic network (~4.4 us per 2048-key sort, after the histogram has been paid): round 2
+// Longest equal-bin run the one-wave sorts fix up by odd-even phases (one phase, when this was measured, ~ 65 slow-rate
+// instructions per lane as compiled; round 7 halved that in the full classes and did not re-measure the threshold)
+// before they prefer the bitonic network (~4.4 us per 2048-key sort, after the histogram has been paid): round 2
 // used 24, which sent 23 % of the slices of the notebooks' cube-surface clouds and 95 % of tightly clustered clouds to
 // the network (profiles/r03_nonuniform.txt).  Measured break-even: ~45 phases (at 64 clouds of 32-fold duplicate
 // points took 0.68 instead of 0.53 ms per launch, at 24 sixteen tight clusters 0.56 instead of 0.52).
@@ -159,6 +164,42 @@ __device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
   x[0] = lo;
 }
 
+// Key policy of the fix-up phases of the FULL classes: the v_min_f32 / v_max_f32 of F32Keys and nothing else.  The
+// kernels run in IEEE mode, where minnum / maxnum must quiet a signalling NaN, and the keys of the fix-up loop are
+// loop-carried values that came out of ds_read_b128: the compiler cannot know them canonical and puts a
+// `v_max_f32 x, y, y` in front of BOTH operands of EVERY compare-exchange.  One loop trip of the headline kernel (two
+// phases: 64 v_min / v_max that do the work) compiled to 130 slow-rate instructions, 66 of them canonicalisations;
+// written as asm the two instructions stand alone: 64 slow-rate instructions per trip (round 7).
+// They are the instructions F32Keys compiles to, so for every key that is no signalling NaN -- -0, denormals (fp32
+// denormals are on), +inf pads, quiet NaNs -- the result has the same bits as before; a signalling NaN is quieted by the
+// v_min / v_max itself, and rows with NaNs have no defined order.  Plain VALU: no wait states, nothing for s_waitcnt; not
+// volatile, so the compiler schedules and removes them like any other pure operation.
+// The classes with pads (binsort_place) and the cooperative sort (coop_sort.hpp) keep F32Keys: not measured with this.
+struct F32KeysRaw {
+  typedef float type;
+  static __device__ __forceinline__ float lo(float a, float b) {
+    float r;
+    asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+  static __device__ __forceinline__ float hi(float a, float b) {
+    float r;
+    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+  }
+};
+
+// binsort_boundary with the compare-exchange of F32KeysRaw
+template <int EPT>
+__device__ __forceinline__ void binsort_boundary_raw(float (&x)[EPT], int lane) {
+  const float nxt = as_f(__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, as_i(x[0])));
+  const float prv = as_f(__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, as_i(x[EPT - 1])));
+  const float hi = F32KeysRaw::lo(x[EPT - 1], lane < 63 ? nxt : __builtin_inff());
+  const float lo = F32KeysRaw::hi(x[0], lane > 0 ? prv : -__builtin_inff());
+  x[EPT - 1] = hi;
+  x[0] = lo;
+}
+
 // Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition
 template <int EPT>
 __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int lane, int g, float* buf) {
@@ -172,11 +213,11 @@ __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int
   // odd-even transposition, g phases (wave-uniform trip count)
   for (int phase = 0; phase < g; phase += 2) {
 #pragma unroll
-    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
+    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
     if (phase + 1 < g) {
 #pragma unroll
-      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
-      binsort_boundary<EPT>(key, lane);
+      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
+      binsort_boundary_raw<EPT>(key, lane);
     }
   }
   __builtin_amdgcn_wave_barrier();
