@@ -27,8 +27,10 @@
 // lane and per loop trip of two phases (31 in-lane compare-exchanges + the one across the lane boundary = 64 v_min /
 // v_max at the source level), as compiled for the headline kernel: up to round 6 130 slow-rate v_min / v_max, 66 of
 // them `v_max x, y, y` canonicalisations of the operands (see F32KeysRaw below; the "33 per phase" of earlier rounds was
-// the source-level count); since round 7, in the full classes, the 64 + 31 full-rate v_mov that rotate the loop's
-// registers (a loop of four phases compiles without them: profiles/r07_forward_summary.txt; not measured, not taken).
+// the source-level count); in round 7, in the full classes, the 64 + 31 full-rate v_mov that rotated the loop's
+// registers; since round 8 the full classes' loop runs four phases per trip, which needs no rotation, and exchanges the
+// keys across the lane boundary by two DPP wave shifts instead of two ds_bpermute and two selects: per trip 124 v_min /
+// v_max + 4 v_min / v_max with DPP + 4 v_mov (binsort_read_back_and_fix; profiles/r08_forward_summary.txt).
 // With g ~ 9 (uniformly spread coordinates) a quarter of the network's VALU work and an eighth of its crossbar traffic.
 // The result is the exact ascending order of the fp32 keys whatever order the atomics were served in.
 // Data with long runs (clustered clouds, duplicates, an all-zero cloud: g > SHW_BINSORT_MAX_RUN) is detected
@@ -49,7 +51,8 @@
 #define SHW_BINSORT_NB_PER_EPT 32
 #endif
 // Longest equal-bin run the one-wave sorts fix up by odd-even phases (one phase, when this was measured, ~ 65 slow-rate
-// instructions per lane as compiled; round 7 halved that in the full classes and did not re-measure the threshold)
+// instructions per lane as compiled; rounds 7 and 8 brought that to 32 in the full classes and did not re-measure the
+// threshold)
 // before they prefer the bitonic network (~4.4 us per 2048-key sort, after the histogram has been paid): round 2
 // used 24, which sent 23 % of the slices of the notebooks' cube-surface clouds and 95 % of tightly clustered clouds to
 // the network (profiles/r03_nonuniform.txt).  Measured break-even: ~45 phases (at 64 clouds of 32-fold duplicate
@@ -71,6 +74,15 @@
 #endif
 #ifndef SHW_COOP_MAX_RUN
 #define SHW_COOP_MAX_RUN 24
+#endif
+// The full classes' fix-up loop (binsort_read_back_and_fix).  1: four phases per trip and the last g mod 4 phases as
+// straight-line code behind wave-uniform branches; 0: the loop of two phases of round 7
+#ifndef SHW_BINSORT_FIX4
+#define SHW_BINSORT_FIX4 1
+#endif
+// 1: the exchange across the lane boundary by two DPP wave shifts (binsort_boundary_dpp); 0: two ds_bpermute and two selects
+#ifndef SHW_BINSORT_DPP_BOUNDARY
+#define SHW_BINSORT_DPP_BOUNDARY 1
 #endif
 
 namespace shw {
@@ -200,6 +212,44 @@ __device__ __forceinline__ void binsort_boundary_raw(float (&x)[EPT], int lane) 
   x[0] = lo;
 }
 
+// binsort_boundary_raw without LDS traffic and without selects: the neighbour's key comes through a DPP wave shift.
+//   hi = v_min_f32_dpp(x[0] of lane + 1, x[EPT-1])   wave_shl:1     lo = v_max_f32_dpp(x[EPT-1] of lane - 1, x[0])   wave_shr:1
+// No bound_ctrl: a lane without a source (63 for the first, 0 for the second) is switched off for that instruction and
+// keeps its destination, which holds its own key on entry ("+" operands) -- what the +-inf selects of the other form
+// give.  Both instructions read the keys as they stand after the odd phase: the destinations are early-clobber copies,
+// never the registers of x[0] / x[EPT-1] themselves.  A DPP operand written by the VALU instruction just before needs two
+// wait states, which the compiler cannot see into an asm block to provide: the s_nop 1 does.  Not volatile, plain "v"
+// operands: scheduled like F32KeysRaw.
+template <int EPT>
+__device__ __forceinline__ void binsort_boundary_dpp(float (&x)[EPT]) {
+  float hi = x[EPT - 1], lo = x[0];
+  asm("s_nop 1\n\t"
+      "v_min_f32_dpp %0, %2, %0 wave_shl:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_max_f32_dpp %1, %3, %1 wave_shr:1 row_mask:0xf bank_mask:0xf"
+      : "+&v"(hi), "+&v"(lo)
+      : "v"(x[0]), "v"(x[EPT - 1]));
+  x[EPT - 1] = hi;
+  x[0] = lo;
+}
+
+// the two phases of the odd-even transposition: pairs (2i, 2i+1) inside a lane; pairs (2i+1, 2i+2) and the pair across
+// every lane boundary
+template <int EPT>
+__device__ __forceinline__ void binsort_even_phase(float (&key)[EPT]) {
+#pragma unroll
+  for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
+}
+template <int EPT>
+__device__ __forceinline__ void binsort_odd_phase(float (&key)[EPT], int lane) {
+#pragma unroll
+  for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
+#if SHW_BINSORT_DPP_BOUNDARY
+  binsort_boundary_dpp<EPT>(key);
+#else
+  binsort_boundary_raw<EPT>(key, lane);
+#endif
+}
+
 // Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition
 template <int EPT>
 __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int lane, int g, float* buf) {
@@ -210,16 +260,33 @@ __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int
     const f32x4 v = *reinterpret_cast<const f32x4*>(bytes + binsort_addr<EPT>(pos0));
     key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
   }
-  // odd-even transposition, g phases (wave-uniform trip count)
-  for (int phase = 0; phase < g; phase += 2) {
-#pragma unroll
-    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
+  // odd-even transposition, g phases: even, odd, even, ... (wave-uniform trip count)
+#if SHW_BINSORT_FIX4
+  // Four phases per trip: a compare-exchange needs a temporary, so the keys leave a phase one register over; after two
+  // phases the compiler copies them back at the loop's back edge (31 v_mov per trip), after four it finds an assignment
+  // that needs no copy.  The last g mod 4 phases are straight-line code behind wave-uniform branches: the keys of paths of
+  // different length meet in different registers, which costs 16 v_mov_b64 at the loop's exit, 16 more for a remainder
+  // of two phases and 32 more for one of three -- once per sort, where the loop of two phases paid 31 v_mov per trip.
+  int phase = 0;
+  for (; phase + 4 <= g; phase += 4) {
+    binsort_even_phase<EPT>(key);
+    binsort_odd_phase<EPT>(key, lane);
+    binsort_even_phase<EPT>(key);
+    binsort_odd_phase<EPT>(key, lane);
+  }
+  if (phase < g) {
+    binsort_even_phase<EPT>(key);
     if (phase + 1 < g) {
-#pragma unroll
-      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
-      binsort_boundary_raw<EPT>(key, lane);
+      binsort_odd_phase<EPT>(key, lane);
+      if (phase + 2 < g) binsort_even_phase<EPT>(key);
     }
   }
+#else
+  for (int phase = 0; phase < g; phase += 2) {
+    binsort_even_phase<EPT>(key);
+    if (phase + 1 < g) binsort_odd_phase<EPT>(key, lane);
+  }
+#endif
   __builtin_amdgcn_wave_barrier();
 }
 
