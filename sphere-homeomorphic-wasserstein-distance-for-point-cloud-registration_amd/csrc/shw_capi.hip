@@ -136,6 +136,39 @@ __global__ __launch_bounds__(256) void stiefel_frames_kernel(const float* __rest
   U[4] = -tau1 * v2; U[5] = q2z;
 }
 
+// ---------------------------------------------------------------------------------------------
+// dispatch: plan (dispatch.hpp), then the launch entry of the planned family's unit
+// ---------------------------------------------------------------------------------------------
+static int launch(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.family) {
+    case Family::forward: return launch_forward(A, P, stream);
+    case Family::forward2: return launch_forward2(A, P, stream);
+    case Family::forward_coop: return launch_forward_coop(A, P, stream);
+    case Family::forward_grad: return launch_forward_grad(A, P, stream);
+    case Family::forward_grad2: return launch_forward_grad2(A, P, stream);
+    case Family::forward_grad2_m32: return launch_forward_grad2_m32(A, P, stream);
+    case Family::forward_grad_coop: return launch_forward_grad_coop(A, P, stream);
+    case Family::forward_grad_kv: return launch_forward_grad_kv(A, P, stream);
+    case Family::level_median: return launch_level_median(A, P, stream);
+    case Family::level_median_merge: return launch_level_median_merge(A, P, stream);
+    case Family::level_median_coop: return launch_level_median_coop(A, P, stream);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+static long problems(const SswArgs& A) { return (long)A.pairs * A.slices; }
+// p != 1, loss only
+static int dispatch_forward(SswArgs& A, hipStream_t stream) { return launch(A, plan_forward(A.n, A.m, problems(A), knobs()), stream); }
+// p != 1, loss + coefficients
+static int dispatch_forward_grad(SswArgs& A, hipStream_t stream) { return launch(A, plan_forward_grad(A.n, A.m, problems(A), knobs()), stream); }
+// p == 1 (coef_s != NULL: + coefficients)
+static int dispatch_level_median(SswArgs& A, hipStream_t stream) { return launch(A, plan_level_median(A.n, A.m, A.coef_s != nullptr, knobs()), stream); }
+// n != m / weights
+static int dispatch_general(SswArgs& A, const float* wu, const float* wv, long wu_pair_stride, long wv_pair_stride,
+                            float* slice_theta, hipStream_t stream) {
+  return launch_general(A, plan_general(A.n, A.m), wu, wv, wu_pair_stride, wv_pair_stride, slice_theta, stream);
+}
+
 }  // namespace shw
 
 extern "C" {
@@ -262,8 +295,12 @@ int shw_ssw_backward_points(const float* xs, const float* xt, const float* dirs,
   if (!xs || !xt || !dirs || !coef_s || !coef_t || !grad_xs || !grad_xt) return (int)hipErrorInvalidValue;
   if (pairs < 0 || slices < 0 || n < 1 || m < 1) return (int)hipErrorInvalidValue;
   if (pairs == 0) return 0;
-  return shw::launch_backward_points(xs, xt, dirs, coef_s, coef_t, pairs, n, m, slices, u_pair_stride, scale, pair_w,
-                                     total_w, grad_xs, grad_xt, (hipStream_t)stream);
+  const bool aligned16 = ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(xt) | reinterpret_cast<uintptr_t>(coef_s) |
+                           reinterpret_cast<uintptr_t>(coef_t) | reinterpret_cast<uintptr_t>(grad_xs) |
+                           reinterpret_cast<uintptr_t>(grad_xt)) & 15) == 0;
+  return shw::launch_backward_points(shw::plan_backward_points(n, m, pairs, slices, aligned16, shw::knobs()), xs, xt, dirs, coef_s,
+                                     coef_t, pairs, n, m, slices, u_pair_stride, scale, pair_w, total_w, grad_xs, grad_xt,
+                                     (hipStream_t)stream);
 }
 
 }  // extern "C"

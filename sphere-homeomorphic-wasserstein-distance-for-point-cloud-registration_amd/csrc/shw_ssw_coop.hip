@@ -128,63 +128,34 @@ __global__ __launch_bounds__(W * 64, FULL ? 1 : 2) void ssw_forward_coop_kernel(
 }
 
 template <int EPT, int W>
-static int launch_forward_coop(SswArgs& A, hipStream_t stream) {
+static int launch_forward_coop_class(SswArgs& A, bool full, hipStream_t stream) {
   typedef Coop<EPT, W> C;
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
-  const bool full = is_pow2(EPT) && (A.n == C::CAP) && (A.m == C::CAP);
-  const dim3 grid((unsigned)total), block(W * 64);
-  if constexpr (is_pow2(EPT)) {                            // (the mask-free forms: power-of-two classes only)
-    if (full) {
-      if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_coop_kernel<EPT, W, 2, true>), grid, block, lds, stream, A);
-      else hipLaunchKernelGGL((ssw_forward_coop_kernel<EPT, W, 0, true>), grid, block, lds, stream, A);
-      return (int)hipGetLastError();
-    }
-  }
-  if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_coop_kernel<EPT, W, 2, false>), grid, block, lds, stream, A);
-  else hipLaunchKernelGGL((ssw_forward_coop_kernel<EPT, W, 0, false>), grid, block, lds, stream, A);
+  const dim3 grid((unsigned)A.num_groups), block(W * 64);
+  with_full<is_pow2(EPT)>(full, [&](auto fl) { with_pmode(A.p_int, [&](auto pm) {   // (mask-free: power-of-two classes)
+    hipLaunchKernelGGL((ssw_forward_coop_kernel<EPT, W, decltype(pm)::value, decltype(fl)::value>), grid, block, lds, stream, A);
+  }); });
   return (int)hipGetLastError();
 }
 
-#ifndef SHW_COOP_EPT
-#define SHW_COOP_EPT 32     // keys per lane (measured at 2048 points: 32 / W=1: 0.267 ms, 16 / W=2: 0.288, 8 / W=4: 0.292)
-#endif
-
-// point count -> cooperative kernel: W = 2 waves per slice up to 4096 points, 4 up to 8192, and 20 / 24 / 32 keys per
-// lane (round 3: a cloud of 3000 points pays for 3072 slots, not 4096; SHW_KPL_CLASSES=0 keeps 32)
-int dispatch_forward_coop(SswArgs& A, hipStream_t stream) {
+// W waves per slice of P.kpl keys per lane: SHW_COOP_EPT / 20 / 24 / 32 above 2048 points, 8 for small grids
+int launch_forward_coop(SswArgs& A, const Plan& P, hipStream_t stream) {
   constexpr int E = SHW_COOP_EPT;
-  const int big = A.n > A.m ? A.n : A.m;
-  const int padded = next_pow2(big);
-  const int W = padded / (64 * E);
-  const int kpl = (W >= 2) ? coop_kpl_for(big, W, false) : E;
-  switch (W * 100 + kpl) {
+  switch (P.waves * 100 + P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT      // developer switch: only the 2048-point class
-    case (2048 / (64 * E)) * 100 + E: return launch_forward_coop<E, 2048 / (64 * E)>(A, stream);
+    case (2048 / (64 * E)) * 100 + E: return launch_forward_coop_class<E, 2048 / (64 * E)>(A, P.full, stream);
 #else
-    case 100 + E: return launch_forward_coop<E, 1>(A, stream);
-    case 220: return launch_forward_coop<20, 2>(A, stream);
-    case 224: return launch_forward_coop<24, 2>(A, stream);
-    case 232: return launch_forward_coop<32, 2>(A, stream);
-    case 420: return launch_forward_coop<20, 4>(A, stream);
-    case 424: return launch_forward_coop<24, 4>(A, stream);
-    case 432: return launch_forward_coop<32, 4>(A, stream);
-#endif
-    default: return (int)hipErrorInvalidValue;
-  }
-}
-
-// Small grids (round 3; see dispatch_forward_grad_small_grid): fewer (pair, slice) problems than SIMDs -- 8 keys per lane,
-// W = padded / 512 waves per slice
-int dispatch_forward_small_grid(SswArgs& A, hipStream_t stream) {
-  const int padded = next_pow2(A.n > A.m ? A.n : A.m);
-  switch (padded / 512) {
-#ifndef SHW_DEV_ONLY_EPT
-    case 1: return launch_forward_coop<8, 1>(A, stream);
-    case 2: return launch_forward_coop<8, 2>(A, stream);
-    case 4: return launch_forward_coop<8, 4>(A, stream);
+    case 100 + E: return launch_forward_coop_class<E, 1>(A, P.full, stream);
+    case 220: return launch_forward_coop_class<20, 2>(A, P.full, stream);
+    case 224: return launch_forward_coop_class<24, 2>(A, P.full, stream);
+    case 232: return launch_forward_coop_class<32, 2>(A, P.full, stream);
+    case 420: return launch_forward_coop_class<20, 4>(A, P.full, stream);
+    case 424: return launch_forward_coop_class<24, 4>(A, P.full, stream);
+    case 432: return launch_forward_coop_class<32, 4>(A, P.full, stream);
+    case 108: return launch_forward_coop_class<8, 1>(A, P.full, stream);
+    case 208: return launch_forward_coop_class<8, 2>(A, P.full, stream);
+    case 408: return launch_forward_coop_class<8, 4>(A, P.full, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "../../include/shw.h"
+#include "dispatch.hpp"      // host launch helpers only: no device code is shared with the float32 units
 
 namespace shw {
 namespace f64 {
@@ -556,12 +557,6 @@ __global__ __launch_bounds__(256) void stiefel_frames_f64_kernel(const double* _
   U[4] = -tau1 * v2; U[5] = q2z;
 }
 
-static int next_pow2(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
 static int small_integer_power(double p) {
   for (int k = 1; k <= 8; ++k)
     if (p == (double)k) return k;
@@ -570,23 +565,16 @@ static int small_integer_power(double p) {
 
 // problems = pairs * slices workgroups; level_median selects the p = 1 formula
 static int launch(Args& A, bool level_median, hipStream_t stream) {
-  const long problems = (long)A.pairs * A.slices;
-  if (problems > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  int problems;
+  if (!problem_groups(A.pairs, A.slices, 1, problems)) return (int)hipErrorInvalidValue;
   A.P = next_pow2(A.n);
   A.p_int = small_integer_power(A.p);
   int threads = A.P / kItems;
   threads = threads < 64 ? 64 : (threads > 1024 ? 1024 : threads);
   const size_t lds = (size_t)A.P * 32 + kFixedLds;
   auto kern = level_median ? ssw_f64_kernel<true> : ssw_f64_kernel<false>;
-  static bool raised[2][64] = {};       // once per kernel and device (not inside a later stream capture)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && !raised[level_median][dev & 63]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    raised[level_median][dev & 63] = true;
-  }
+  if (const hipError_t e = level_median ? raise_dynamic_lds<ssw_f64_kernel<true>>(lds) : raise_dynamic_lds<ssw_f64_kernel<false>>(lds))
+    return (int)e;
   hipLaunchKernelGGL(kern, dim3((unsigned)problems), dim3(threads), lds, stream, A);
   return (int)hipGetLastError();
 }

@@ -1,6 +1,4 @@
 // shw_ssw_fwd.hip -- loss-only kernel for p != 1 (key-only register sort).  See ssw_common.hpp.
-#include <cstdlib>
-
 #include "ssw_common.hpp"
 #include "bin_sort.hpp"
 
@@ -260,115 +258,49 @@ __global__ __launch_bounds__(W * 64, 4) void ssw_forward_mw_kernel(SswArgs A) {
 }
 
 template <int W>
-static int launch_forward_mw(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+static int launch_forward_mw(SswArgs& A, bool full, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(32 * 64 * W + 4 * W) * sizeof(float);
-  const bool full = (A.n == 2048 * W) && (A.m == 2048 * W);
-  const dim3 grid((unsigned)total), block(W * 64);
-  if (A.p_int == 2) {
-    if (full) hipLaunchKernelGGL((ssw_forward_mw_kernel<W, 2, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_mw_kernel<W, 2, false>), grid, block, lds, stream, A);
-  } else {
-    if (full) hipLaunchKernelGGL((ssw_forward_mw_kernel<W, 0, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_mw_kernel<W, 0, false>), grid, block, lds, stream, A);
-  }
+  const dim3 grid((unsigned)A.num_groups), block(W * 64);
+  with_pmode(A.p_int, [&](auto pm) { with_full(full, [&](auto fl) {
+    hipLaunchKernelGGL((ssw_forward_mw_kernel<W, decltype(pm)::value, decltype(fl)::value>), grid, block, lds, stream, A);
+  }); });
   return (int)hipGetLastError();
 }
 
 template <int EPT, int WAVES>
-static int launch_forward(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  const long groups = (total + WAVES - 1) / WAVES;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
+static int launch_forward_class(SswArgs& A, bool full, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, WAVES, A.num_groups)) return (int)hipErrorInvalidValue;
   size_t lds = (size_t)WAVES * forward_lds_floats(EPT) * sizeof(float);
 #ifdef SHW_DEV_OCCUPANCY_EXPERIMENT   // developer build only: pad the LDS request to lower the waves per CU
   if (const char* extra = getenv("SHW_DEV_EXTRA_LDS")) lds += (size_t)atoi(extra);
 #endif
-  const bool full = (A.n == EPT * kWave) && (A.m == EPT * kWave);
-  const dim3 grid((unsigned)groups), block(WAVES * 64);
-  if (A.p_int == 2) {
-    if (full) hipLaunchKernelGGL((ssw_forward_kernel<EPT, WAVES, 2, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_kernel<EPT, WAVES, 2, false>), grid, block, lds, stream, A);
-  } else {
-    if (full) hipLaunchKernelGGL((ssw_forward_kernel<EPT, WAVES, 0, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_kernel<EPT, WAVES, 0, false>), grid, block, lds, stream, A);
-  }
+  const dim3 grid((unsigned)A.num_groups), block(WAVES * 64);
+  with_pmode(A.p_int, [&](auto pm) { with_full(full, [&](auto fl) {
+    hipLaunchKernelGGL((ssw_forward_kernel<EPT, WAVES, decltype(pm)::value, decltype(fl)::value>), grid, block, lds, stream, A);
+  }); });
   return (int)hipGetLastError();
 }
 
-int dispatch_forward_coop(SswArgs& A, hipStream_t stream);       // shw_ssw_coop.hip
-int dispatch_forward2(SswArgs& A, hipStream_t stream);           // shw_ssw_fwd2.hip
-
-// Which loss-only kernel serves p != 1 (measured, profiles/r02_ab_twowave_fwd.txt):
-//   n == m == 2048 exactly    : one wave per slice (ssw_forward_kernel, in-wave distribution sort) -- 0.228 ms at config 3
-//                               against 0.240 for two waves (round 4: 0.207, and no longer spilling)
-//   512..2048 (padded) points : otherwise two waves per slice, one cloud each (shw_ssw_fwd2.hip): no spills, and faster
-//                               wherever the cloud does not fill its size class (N=2000: 0.306 vs 0.330 ms)
-//   > 2048                    : W = padded / 2048 waves per slice, cooperative distribution sort (shw_ssw_coop.hip)
-//   < 512                     : one wave per slice, register network below 8 keys per lane
-// SHW_FORWARD_KERNEL (diagnostic, read once; the tests run every family): onewave = never two waves;
-// twowave = two waves also at 2048 exactly; network = the bitonic multi-wave kernel above 2048 points;
-// coop = the cooperative kernel from 2048 points on.
-static int forward_family() {
-  static const int fam = [] {
-    const char* e = getenv("SHW_FORWARD_KERNEL");
-    if (e && e[0] == 'n') return 1;       // network
-    if (e && e[0] == 'c') return 2;       // coop from 2048
-    if (e && e[0] == 't') return 3;       // twowave
-    if (e && e[0] == 'o') return 4;       // onewave
-    return 0;
-  }();
-  return fam;
-}
-
-int dispatch_forward_small_grid(SswArgs& A, hipStream_t stream);   // shw_ssw_coop.hip
-
-// launches with at most this many (pair, slice) problems take the small-grid kernels (SHW_SMALL_GRID overrides; 0 = never)
-static long small_grid_slices() {
-  static const long v = [] {
-    const char* e = getenv("SHW_SMALL_GRID");
-    return e ? atol(e) : 1024L;
-  }();
-  return v;
-}
-
-int dispatch_forward(SswArgs& A, hipStream_t stream) {
-#ifndef SHW_NO_COOP
-  {
-    const int padded = next_pow2(A.n > A.m ? A.n : A.m);
-    const int fam = forward_family();
-    // fewer problems than SIMDs: latency-bound, W waves per slice of 8 keys per lane
-    if (fam == 0 && padded >= 512 && padded <= 2048 && (long)A.pairs * A.slices <= small_grid_slices())
-      return dispatch_forward_small_grid(A, stream);
-    if ((fam == 0 && padded > 2048) || (fam == 2 && padded >= 2048)) return dispatch_forward_coop(A, stream);
-    if (padded >= 512 && padded <= 2048 && fam != 4 && fam != 1) {
-      const bool headline = (A.n == 2048 && A.m == 2048);
-      if (fam == 3 || (fam == 0 && !headline)) return dispatch_forward2(A, stream);
-    }
-  }
-#endif
-  switch (ept_for(A.n, A.m)) {
+int launch_forward(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT   // developer switch: compile a single size class quickly
 #ifndef SHW_DEV_FWD_WAVES
 #define SHW_DEV_FWD_WAVES (SHW_DEV_ONLY_EPT <= 32 ? SHW_FWD_WAVES : (SHW_DEV_ONLY_EPT == 64 ? 2 : 1))
 #endif
-    case SHW_DEV_ONLY_EPT: return launch_forward<SHW_DEV_ONLY_EPT, SHW_DEV_FWD_WAVES>(A, stream);
+    case SHW_DEV_ONLY_EPT: return launch_forward_class<SHW_DEV_ONLY_EPT, SHW_DEV_FWD_WAVES>(A, P.full, stream);
 #else
-    case 1: return launch_forward<1, 4>(A, stream);
-    case 2: return launch_forward<2, 4>(A, stream);
-    case 4: return launch_forward<4, 4>(A, stream);
-    case 8: return launch_forward<8, 4>(A, stream);
-    case 16: return launch_forward<16, 4>(A, stream);
-    case 32: return launch_forward<32, SHW_FWD_WAVES>(A, stream);
-    case 64: return launch_forward_mw<2>(A, stream);            // 2049..4096 points: two waves per slice
-    case 128: return launch_forward_mw<4>(A, stream);           // 4097..8192 points: four waves per slice
+    case 1: return launch_forward_class<1, 4>(A, P.full, stream);
+    case 2: return launch_forward_class<2, 4>(A, P.full, stream);
+    case 4: return launch_forward_class<4, 4>(A, P.full, stream);
+    case 8: return launch_forward_class<8, 4>(A, P.full, stream);
+    case 16: return launch_forward_class<16, 4>(A, P.full, stream);
+    case 32: return launch_forward_class<32, SHW_FWD_WAVES>(A, P.full, stream);
+    case 64: return launch_forward_mw<2>(A, P.full, stream);            // 2049..4096 points: two waves per slice
+    case 128: return launch_forward_mw<4>(A, P.full, stream);           // 4097..8192 points: four waves per slice
 #endif
     default: return (int)hipErrorInvalidValue;
   }
 }
-
 
 }  // namespace shw

@@ -112,38 +112,28 @@ __global__ __launch_bounds__(128, SHW_FWD2_MINW) void ssw_forward2_kernel(SswArg
 }
 
 template <int EPT>
-static int launch_forward2(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+static int launch_forward2_class(SswArgs& A, bool full, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(2 * (binsort_bins<EPT>() + 64 * EPT) + 32) * sizeof(float);
-  // (the mask-free forms index with shifts and masks: power-of-two classes only)
-  const bool full = is_pow2(EPT) && (A.n == EPT * kWave) && (A.m == EPT * kWave);
-  const dim3 grid((unsigned)total), block(128);
-  if constexpr (is_pow2(EPT)) {
-    if (full) {
-      if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward2_kernel<EPT, 2, true>), grid, block, lds, stream, A);
-      else hipLaunchKernelGGL((ssw_forward2_kernel<EPT, 0, true>), grid, block, lds, stream, A);
-      return (int)hipGetLastError();
-    }
-  }
-  if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward2_kernel<EPT, 2, false>), grid, block, lds, stream, A);
-  else hipLaunchKernelGGL((ssw_forward2_kernel<EPT, 0, false>), grid, block, lds, stream, A);
+  const dim3 grid((unsigned)A.num_groups), block(128);
+  with_full<is_pow2(EPT)>(full, [&](auto fl) { with_pmode(A.p_int, [&](auto pm) {
+    hipLaunchKernelGGL((ssw_forward2_kernel<EPT, decltype(pm)::value, decltype(fl)::value>), grid, block, lds, stream, A);
+  }); });
   return (int)hipGetLastError();
 }
 
-int dispatch_forward2(SswArgs& A, hipStream_t stream) {
-  switch (kpl_for(A.n, A.m)) {
+int launch_forward2(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_forward2<SHW_DEV_ONLY_EPT>(A, stream);
+    case SHW_DEV_ONLY_EPT: return launch_forward2_class<SHW_DEV_ONLY_EPT>(A, P.full, stream);
 #else
-    case 8: return launch_forward2<8>(A, stream);
-    case 12: return launch_forward2<12>(A, stream);
-    case 16: return launch_forward2<16>(A, stream);
-    case 20: return launch_forward2<20>(A, stream);
-    case 24: return launch_forward2<24>(A, stream);
-    case 28: return launch_forward2<28>(A, stream);
-    case 32: return launch_forward2<32>(A, stream);
+    case 8: return launch_forward2_class<8>(A, P.full, stream);
+    case 12: return launch_forward2_class<12>(A, P.full, stream);
+    case 16: return launch_forward2_class<16>(A, P.full, stream);
+    case 20: return launch_forward2_class<20>(A, P.full, stream);
+    case 24: return launch_forward2_class<24>(A, P.full, stream);
+    case 28: return launch_forward2_class<28>(A, P.full, stream);
+    case 32: return launch_forward2_class<32>(A, P.full, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

@@ -1880,13 +1880,11 @@ __global__ __launch_bounds__(128, 2) void ssw_general_p1_walk2_kernel(GeneralArg
 }
 
 template <int EPT>
-static int launch_general(GeneralArgs& G, hipStream_t stream) {
+static int launch_general_class(GeneralArgs& G, hipStream_t stream) {
   SswArgs& A = G.base;
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const bool grad = A.coef_s != nullptr;
-  const dim3 grid((unsigned)total), block(64);
+  const dim3 grid((unsigned)A.num_groups), block(64);
   if (A.p == 1.f && !A.bisect_p1) {
     if constexpr (EPT >= 8) {
       const size_t lds2 = ((size_t)(grad ? 6 : 4) * EPT * kWave + 2 * kWalkExt * kWave + kTeamFloats) * sizeof(float);
@@ -1937,16 +1935,11 @@ static int launch_general(GeneralArgs& G, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
-static int gcd_general(int a, int b) {
-  while (b) { const int t = a % b; a = b; b = t; }
-  return a;
-}
-
-int dispatch_general(SswArgs& A, const float* wu, const float* wv, long wu_pair_stride, long wv_pair_stride,
-                     float* slice_theta, hipStream_t stream) {
+int launch_general(SswArgs& A, const Plan& P, const float* wu, const float* wv, long wu_pair_stride, long wv_pair_stride,
+                   float* slice_theta, hipStream_t stream) {
   GeneralArgs G{A, wu, wv, wu_pair_stride, wv_pair_stride, slice_theta, 0.f, 0.f, 0, 0, 0, nullptr, nullptr, 0, 0, 0};
   if (wu == nullptr && wv == nullptr) {                      // no weights: the integer grid of lcm(n, m)
-    const long lcm = (long)A.n / gcd_general(A.n, A.m) * (long)A.m;
+    const long lcm = (long)A.n / gcd(A.n, A.m) * (long)A.m;
     G.lcm = (int)lcm;                                        // n, m <= 4096: < 2^24
     G.lcm_a = G.lcm / A.n;
     G.lcm_b = G.lcm / A.m;
@@ -1954,17 +1947,17 @@ int dispatch_general(SswArgs& A, const float* wu, const float* wv, long wu_pair_
     G.first_step = 0.25f / (float)(A.n + A.m);
     G.min_width = 1e-7f;                                     // eps / L, :189
   }
-  switch (ept_for(A.n, A.m)) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_general<SHW_DEV_ONLY_EPT>(G, stream);
+    case SHW_DEV_ONLY_EPT: return launch_general_class<SHW_DEV_ONLY_EPT>(G, stream);
 #else
-    case 1: return launch_general<1>(G, stream);
-    case 2: return launch_general<2>(G, stream);
-    case 4: return launch_general<4>(G, stream);
-    case 8: return launch_general<8>(G, stream);
-    case 16: return launch_general<16>(G, stream);
-    case 32: return launch_general<32>(G, stream);
-    case 64: return launch_general<64>(G, stream);
+    case 1: return launch_general_class<1>(G, stream);
+    case 2: return launch_general_class<2>(G, stream);
+    case 4: return launch_general_class<4>(G, stream);
+    case 8: return launch_general_class<8>(G, stream);
+    case 16: return launch_general_class<16>(G, stream);
+    case 32: return launch_general_class<32>(G, stream);
+    case 64: return launch_general_class<64>(G, stream);
 #endif
     default: return (int)hipErrorInvalidValue;               // > 4096 points: not built for this path
   }

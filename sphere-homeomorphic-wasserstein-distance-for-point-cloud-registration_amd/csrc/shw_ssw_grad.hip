@@ -332,111 +332,52 @@ __global__ __launch_bounds__(64 * SHW_BWD4_WAVES) void ssw_backward_points4_kern
   }
 }
 
-int launch_forward_grad_kv128(SswArgs& A, hipStream_t stream);
-
 template <int EPT, int WAVES>
-static int launch_forward_grad(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  const long groups = (total + WAVES - 1) / WAVES;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
+static int launch_forward_grad_class(SswArgs& A, bool full, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, WAVES, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)WAVES * (EPT * kWave * 6);
-  const bool full = (A.n == EPT * kWave) && (A.m == EPT * kWave);
-  const dim3 grid((unsigned)groups), block(WAVES * 64);
-  if (A.p_int == 2) {
-    if (full) hipLaunchKernelGGL((ssw_forward_grad_kernel<EPT, WAVES, 2, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_grad_kernel<EPT, WAVES, 2, false>), grid, block, lds, stream, A);
-  } else {
-    if (full) hipLaunchKernelGGL((ssw_forward_grad_kernel<EPT, WAVES, 0, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_grad_kernel<EPT, WAVES, 0, false>), grid, block, lds, stream, A);
-  }
+  const dim3 grid((unsigned)A.num_groups), block(WAVES * 64);
+  with_pmode(A.p_int, [&](auto pm) { with_full(full, [&](auto fl) {
+    hipLaunchKernelGGL((ssw_forward_grad_kernel<EPT, WAVES, decltype(pm)::value, decltype(fl)::value>), grid, block, lds, stream, A);
+  }); });
   return (int)hipGetLastError();
 }
 
-// SHW_GRAD_KERNEL=onewave (diagnostic, used by the tests): the one-wave kernel of this file at every size
-static bool grad_one_wave_forced() {
-  static const bool forced = [] { const char* e = getenv("SHW_GRAD_KERNEL"); return e && e[0] == 'o'; }();
-  return forced;
-}
-
-int dispatch_forward_grad_small_grid(SswArgs& A, hipStream_t stream);   // shw_ssw_grad_coop.hip
-
-// launches with at most this many (pair, slice) problems take the small-grid kernels (SHW_SMALL_GRID overrides; 0 = never)
-static long small_grid_slices() {
-  static const long v = [] {
-    const char* e = getenv("SHW_SMALL_GRID");
-    return e ? atol(e) : 1024L;
-  }();
-  return v;
-}
-
-int dispatch_forward_grad(SswArgs& A, hipStream_t stream) {
-  {
-    const int ept = ept_for(A.n, A.m);
-    // fewer problems than SIMDs: latency-bound, W waves per slice (shw_ssw_grad_coop.hip, small grids)
-    if (ept >= 8 && ept <= 32 && (long)A.pairs * A.slices <= small_grid_slices() && !grad_one_wave_forced())
-      return dispatch_forward_grad_small_grid(A, stream);
-    if (ept >= 8 && ept <= 32 && !grad_one_wave_forced()) return dispatch_forward_grad2(A, stream);   // shw_ssw_grad2.hip
-    if ((ept == 64 || ept == 128) && !grad_one_wave_forced()) return dispatch_forward_grad_coop(A, stream);   // shw_ssw_grad_coop.hip
-  }
-  switch (ept_for(A.n, A.m)) {
+int launch_forward_grad(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_forward_grad<SHW_DEV_ONLY_EPT, 1>(A, stream);
+    case SHW_DEV_ONLY_EPT: return launch_forward_grad_class<SHW_DEV_ONLY_EPT, 1>(A, P.full, stream);
 #else
-    case 1: return launch_forward_grad<1, 4>(A, stream);
-    case 2: return launch_forward_grad<2, 4>(A, stream);
-    case 4: return launch_forward_grad<4, 4>(A, stream);
-    case 8: return launch_forward_grad<8, 4>(A, stream);
-    case 16: return launch_forward_grad<16, 4>(A, stream);
-    case 32: return launch_forward_grad<32, 1>(A, stream);
-    case 64: return launch_forward_grad<64, 1>(A, stream);
-    case 128: return launch_forward_grad_kv128(A, stream);      // shw_ssw_grad_kv.hip
+    case 1: return launch_forward_grad_class<1, 4>(A, P.full, stream);
+    case 2: return launch_forward_grad_class<2, 4>(A, P.full, stream);
+    case 4: return launch_forward_grad_class<4, 4>(A, P.full, stream);
+    case 8: return launch_forward_grad_class<8, 4>(A, P.full, stream);
+    case 16: return launch_forward_grad_class<16, 4>(A, P.full, stream);
+    case 32: return launch_forward_grad_class<32, 1>(A, P.full, stream);
+    case 64: return launch_forward_grad_class<64, 1>(A, P.full, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }
 }
 
-
-int launch_backward_points(const float* xs, const float* xt, const float* dirs, const float* coef_s,
-                           const float* coef_t, int pairs, int n, int m, int slices, long u_pair_stride,
-                           float scale, const float* pair_w, const float* total_w, float* grad_xs, float* grad_xt,
-                           hipStream_t stream) {
-  // sizes that are multiples of 4 (16-byte aligned rows and points): four points per lane, 16-byte loads
-  // SHW_BWD_WIDE=0: never; =2: whenever sizes and alignment allow (tests); default: when the grid also fills the chip
-  static const int wide_mode = [] { const char* v = getenv("SHW_BWD_WIDE"); return v ? (v[0] == '0' ? 0 : (v[0] == '2' ? 2 : 1)) : 1; }();
-  const bool wide_ok = wide_mode != 0;
-  const bool aligned = ((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(xt) | reinterpret_cast<uintptr_t>(coef_s) |
-                         reinterpret_cast<uintptr_t>(coef_t) | reinterpret_cast<uintptr_t>(grad_xs) |
-                         reinterpret_cast<uintptr_t>(grad_xt)) & 15) == 0;
-  // ... and launches that fill the chip with 256-point workgroups (two per CU): a small grid -- the notebooks' one pair of
-  // 1200 points -- is latency, and the one-point-per-lane kernel has four times the workgroups (9.3 against 15.2 us there)
-  const long wide_groups = (long)((n + 255) / 256 + (m + 255) / 256) * pairs;
-  if (wide_ok && aligned && n % 4 == 0 && m % 4 == 0 && n >= 4 && m >= 4 && (wide_groups >= 512 || wide_mode == 2)) {
-    const int c_s = (n + 255) / 256, c_t = (m + 255) / 256;
-    for (int b0 = 0; b0 < pairs; b0 += 65535) {
-      const int nb = pairs - b0 < 65535 ? pairs - b0 : 65535;
-      hipLaunchKernelGGL(ssw_backward_points4_kernel, dim3(c_s + c_t, nb), dim3(64 * SHW_BWD4_WAVES), 0, stream,
-                         xs + (long)b0 * n * 3, xt + (long)b0 * m * 3, dirs + (long)b0 * u_pair_stride,
-                         coef_s + (long)b0 * slices * n, coef_t + (long)b0 * slices * m, n, m, slices, u_pair_stride,
-                         scale, pair_w ? pair_w + b0 : nullptr, total_w, grad_xs + (long)b0 * n * 3, grad_xt + (long)b0 * m * 3, c_s);
-    }
-    return (int)hipGetLastError();
-  }
-  const int chunks_s = (n + 63) / 64, chunks_t = (m + 63) / 64;
-  // pairs ride on gridDim.y (<= 65535): larger batches go out as several launches over pair blocks
+// pairs ride on gridDim.y (<= 65535): larger batches go out as several launches over pair blocks
+int launch_backward_points(const Plan& P, const float* xs, const float* xt, const float* dirs, const float* coef_s,
+                           const float* coef_t, int pairs, int n, int m, int slices, long u_pair_stride, float scale,
+                           const float* pair_w, const float* total_w, float* grad_xs, float* grad_xt, hipStream_t stream) {
+  const int points = P.family == Family::backward_points4 ? 256 : 64;      // of a workgroup
+  const int chunks_s = (n + points - 1) / points, chunks_t = (m + points - 1) / points;
   for (int b0 = 0; b0 < pairs; b0 += 65535) {
     const int nb = pairs - b0 < 65535 ? pairs - b0 : 65535;
-    // fewer workgroups than CUs: sixteen waves per workgroup share the slices
-    if ((long)(chunks_s + chunks_t) * pairs < 256 && slices >= 32)
-      hipLaunchKernelGGL(ssw_backward_points_kernel<16>, dim3(chunks_s + chunks_t, nb), dim3(1024), 0, stream,
-                         xs + (long)b0 * n * 3, xt + (long)b0 * m * 3, dirs + (long)b0 * u_pair_stride,
-                         coef_s + (long)b0 * slices * n, coef_t + (long)b0 * slices * m, n, m, slices, u_pair_stride,
-                         scale, pair_w ? pair_w + b0 : nullptr, total_w, grad_xs + (long)b0 * n * 3, grad_xt + (long)b0 * m * 3, chunks_s);
-    else
-      hipLaunchKernelGGL(ssw_backward_points_kernel<4>, dim3(chunks_s + chunks_t, nb), dim3(256), 0, stream,
-                         xs + (long)b0 * n * 3, xt + (long)b0 * m * 3, dirs + (long)b0 * u_pair_stride,
-                         coef_s + (long)b0 * slices * n, coef_t + (long)b0 * slices * m, n, m, slices, u_pair_stride,
-                         scale, pair_w ? pair_w + b0 : nullptr, total_w, grad_xs + (long)b0 * n * 3, grad_xt + (long)b0 * m * 3, chunks_s);
+    const dim3 grid(chunks_s + chunks_t, nb);
+#define SHW_LAUNCH_BACKWARD(KERNEL, WAVES)                                                                                \
+    hipLaunchKernelGGL(KERNEL, grid, dim3(64 * (WAVES)), 0, stream, xs + (long)b0 * n * 3, xt + (long)b0 * m * 3,           \
+                       dirs + (long)b0 * u_pair_stride, coef_s + (long)b0 * slices * n, coef_t + (long)b0 * slices * m, n, m, \
+                       slices, u_pair_stride, scale, pair_w ? pair_w + b0 : nullptr, total_w, grad_xs + (long)b0 * n * 3,   \
+                       grad_xt + (long)b0 * m * 3, chunks_s)
+    if (P.family == Family::backward_points4) SHW_LAUNCH_BACKWARD(ssw_backward_points4_kernel, SHW_BWD4_WAVES);
+    else if (P.waves == 16) SHW_LAUNCH_BACKWARD(ssw_backward_points_kernel<16>, 16);
+    else SHW_LAUNCH_BACKWARD(ssw_backward_points_kernel<4>, 4);
+#undef SHW_LAUNCH_BACKWARD
   }
   return (int)hipGetLastError();
 }

@@ -158,57 +158,41 @@ __global__ __launch_bounds__(128, grad2_waves_per_simd(EPT, FULL)) void ssw_forw
 // compiled with SHW_GRAD2_MASKED32_UNIT): it is the one kernel of the library that is faster WITH the compiler's SLP
 // vectorisation (without the packed forms it spills 45 registers: N = 2000 training step 0.62 -> 0.74 ms), every other
 // instantiation is built with -fno-slp-vectorize like the rest of the library (Makefile, SLP_UNITS).
-#ifdef SHW_GRAD2_MASKED32_UNIT
-int launch_forward_grad2_masked32(SswArgs& A, hipStream_t stream) {
-  constexpr int EPT = 32;
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+template <int EPT, bool FULL>
+static int launch_forward_grad2_class(SswArgs& A, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(2 * (EPT * kWave + grad2_counter_floats(EPT)) + 32) * sizeof(float);
-  const dim3 grid((unsigned)total), block(128);
-  if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 2, false>), grid, block, lds, stream, A);
-  else hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 0, false>), grid, block, lds, stream, A);
+  const dim3 grid((unsigned)A.num_groups), block(128);
+  if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 2, FULL>), grid, block, lds, stream, A);
+  else hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 0, FULL>), grid, block, lds, stream, A);
   return (int)hipGetLastError();
 }
-#else
-int launch_forward_grad2_masked32(SswArgs& A, hipStream_t stream);   // shw_ssw_grad2_m32.hip
 
+#ifdef SHW_GRAD2_MASKED32_UNIT
+int launch_forward_grad2_m32(SswArgs& A, const Plan& P, hipStream_t stream) {
+  return P.kpl == 32 && !P.full ? launch_forward_grad2_class<32, false>(A, stream) : (int)hipErrorInvalidValue;
+}
+#else
 template <int EPT>
-static int launch_forward_grad2(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
-  const size_t lds = (size_t)(2 * (EPT * kWave + grad2_counter_floats(EPT)) + 32) * sizeof(float);
-  // (the mask-free forms index with shifts and masks: power-of-two classes only)
-  const bool full = is_pow2(EPT) && (A.n == EPT * kWave) && (A.m == EPT * kWave);
-  const dim3 grid((unsigned)total), block(128);
+static int launch_forward_grad2_either(SswArgs& A, bool full, hipStream_t stream) {
   if constexpr (is_pow2(EPT)) {
-    if (full) {
-      if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 2, true>), grid, block, lds, stream, A);
-      else hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 0, true>), grid, block, lds, stream, A);
-      return (int)hipGetLastError();
-    }
+    if (full) return launch_forward_grad2_class<EPT, true>(A, stream);
   }
-  if constexpr (EPT == 32) {
-    return launch_forward_grad2_masked32(A, stream);
-  } else {
-    if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 2, false>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((ssw_forward_grad2_kernel<EPT, 0, false>), grid, block, lds, stream, A);
-    return (int)hipGetLastError();
-  }
+  if constexpr (EPT == 32) return (int)hipErrorInvalidValue;             // (planned as forward_grad2_m32)
+  else return launch_forward_grad2_class<EPT, false>(A, stream);
 }
 
-int dispatch_forward_grad2(SswArgs& A, hipStream_t stream) {
-  switch (kpl_for(A.n, A.m, true)) {
+int launch_forward_grad2(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_forward_grad2<SHW_DEV_ONLY_EPT>(A, stream);
+    case SHW_DEV_ONLY_EPT: return launch_forward_grad2_either<SHW_DEV_ONLY_EPT>(A, P.full, stream);
 #else
-    case 8: return launch_forward_grad2<8>(A, stream);
-    case 12: return launch_forward_grad2<12>(A, stream);
-    case 16: return launch_forward_grad2<16>(A, stream);
-    case 20: return launch_forward_grad2<20>(A, stream);
-    case 24: return launch_forward_grad2<24>(A, stream);
-    case 32: return launch_forward_grad2<32>(A, stream);
+    case 8: return launch_forward_grad2_either<8>(A, P.full, stream);
+    case 12: return launch_forward_grad2_either<12>(A, P.full, stream);
+    case 16: return launch_forward_grad2_either<16>(A, P.full, stream);
+    case 20: return launch_forward_grad2_either<20>(A, P.full, stream);
+    case 24: return launch_forward_grad2_either<24>(A, P.full, stream);
+    case 32: return launch_forward_grad2_either<32>(A, P.full, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

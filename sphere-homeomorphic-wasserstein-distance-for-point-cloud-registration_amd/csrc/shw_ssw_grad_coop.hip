@@ -190,69 +190,31 @@ __global__ __launch_bounds__(W * 64, W == 2 ? SHW_GRADCOOP_MINW : 1) void ssw_fo
 }
 
 template <int EPT, int W>
-static int launch_forward_grad_coop(SswArgs& A, hipStream_t stream) {
+static int launch_forward_grad_coop_class(SswArgs& A, bool full, hipStream_t stream) {
   typedef Coop<EPT, W> C;
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)(3 * C::CAP + C::RED) * sizeof(float);
-  const bool full = is_pow2(EPT) && (A.n == C::CAP) && (A.m == C::CAP);
-  const dim3 grid((unsigned)total), block(W * 64);
-#define SHW_LAUNCH_GRAD_COOP(PM, FL)                                                                              \
-  do {                                                                                                            \
-    auto kern = ssw_forward_grad_coop_kernel<EPT, W, PM, FL>;                                                     \
-    static bool raised[64] = {};      /* once per instantiation and device (not inside a later stream capture) */   \
-    int dev_ = 0;                                                                                                 \
-    (void)hipGetDevice(&dev_);                                                                                    \
-    if (lds > 64 * 1024 && !raised[dev_ & 63]) {                                                                  \
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
-      if (e != hipSuccess) return (int)e;                                                                         \
-      raised[dev_ & 63] = true;                                                                                   \
-    }                                                                                                             \
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, A);                                                        \
-  } while (0)
-  if constexpr (is_pow2(EPT)) {                            // (the mask-free forms: power-of-two classes only)
-    if (full) {
-      if (A.p_int == 2) SHW_LAUNCH_GRAD_COOP(2, true); else SHW_LAUNCH_GRAD_COOP(0, true);
-      return (int)hipGetLastError();
-    }
-  }
-  if (A.p_int == 2) SHW_LAUNCH_GRAD_COOP(2, false); else SHW_LAUNCH_GRAD_COOP(0, false);
-#undef SHW_LAUNCH_GRAD_COOP
-  return (int)hipGetLastError();
+  hipError_t raised = hipSuccess;
+  with_full<is_pow2(EPT)>(full, [&](auto fl) { with_pmode(A.p_int, [&](auto pm) {   // (mask-free: power-of-two classes)
+    constexpr auto kern = ssw_forward_grad_coop_kernel<EPT, W, decltype(pm)::value, decltype(fl)::value>;
+    raised = raise_dynamic_lds<kern>(lds);
+    if (raised == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)A.num_groups), dim3(W * 64), lds, stream, A);
+  }); });
+  return raised != hipSuccess ? (int)raised : (int)hipGetLastError();
 }
 
-// 2049..4096 points: W = 2 waves per slice, 4097..8192: W = 4; 20 / 24 / 32 atoms per lane (round 3: 3000 points pay
-// for 3072 slots, 5000 for 5120)
-int dispatch_forward_grad_coop(SswArgs& A, hipStream_t stream) {
-  if (A.n != A.m) return (int)hipErrorInvalidValue;
-  const int W = next_pow2(A.n) / 2048;
-  switch (W * 100 + coop_kpl_for(A.n, W, true)) {
+// W = 2 / 4 waves per slice of 20 / 24 / 32 atoms per lane above 2048 points; 8 atoms per lane for small grids
+int launch_forward_grad_coop(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.waves * 100 + P.kpl) {
 #ifndef SHW_DEV_ONLY_EPT
-    case 220: return launch_forward_grad_coop<20, 2>(A, stream);
-    case 224: return launch_forward_grad_coop<24, 2>(A, stream);
-    case 232: return launch_forward_grad_coop<32, 2>(A, stream);
-    case 420: return launch_forward_grad_coop<20, 4>(A, stream);
-    case 432: return launch_forward_grad_coop<32, 4>(A, stream);
-#endif
-    default: return (int)hipErrorInvalidValue;
-  }
-}
-
-// Small grids (round 3): when a launch has fewer (pair, slice) problems than the chip has SIMDs -- the notebooks' gradient
-// flow is ONE pair x 100 slices (Flow_cube.ipynb:1381) -- a slice is latency, not throughput: 8 atoms per lane and
-// W = padded / 512 waves per slice (4 at 1025..2048 points) cut the dependent chain of the sort and the solve and put
-// 400 waves on the chip instead of 200.  (For full grids the same form is slower: wave scans, barriers and the seam sort
-// are paid W times -- profiles/r02_ab_coop_keys_per_lane.txt.)
-int dispatch_forward_grad_small_grid(SswArgs& A, hipStream_t stream) {
-  if (A.n != A.m) return (int)hipErrorInvalidValue;
-  const int padded = next_pow2(A.n);
-  switch (padded / 512) {
-#ifndef SHW_DEV_ONLY_EPT
-    case 1: return launch_forward_grad_coop<8, 1>(A, stream);
-    case 2: return launch_forward_grad_coop<8, 2>(A, stream);
-    case 4: return launch_forward_grad_coop<8, 4>(A, stream);
+    case 220: return launch_forward_grad_coop_class<20, 2>(A, P.full, stream);
+    case 224: return launch_forward_grad_coop_class<24, 2>(A, P.full, stream);
+    case 232: return launch_forward_grad_coop_class<32, 2>(A, P.full, stream);
+    case 420: return launch_forward_grad_coop_class<20, 4>(A, P.full, stream);
+    case 432: return launch_forward_grad_coop_class<32, 4>(A, P.full, stream);
+    case 108: return launch_forward_grad_coop_class<8, 1>(A, P.full, stream);
+    case 208: return launch_forward_grad_coop_class<8, 2>(A, P.full, stream);
+    case 408: return launch_forward_grad_coop_class<8, 4>(A, P.full, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

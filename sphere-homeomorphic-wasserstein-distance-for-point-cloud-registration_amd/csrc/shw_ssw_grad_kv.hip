@@ -78,17 +78,13 @@ __global__ __launch_bounds__(WAVES * 64) void ssw_forward_grad_kv_kernel(SswArgs
   }
 }
 
-int launch_forward_grad_kv128(SswArgs& A, hipStream_t stream) {
+int launch_forward_grad_kv(SswArgs& A, const Plan& P, hipStream_t stream) {
   constexpr int EPT = 128, WAVES = 1;
-  const long groups = (long)A.pairs * A.slices;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
+  if (P.kpl != EPT || !problem_groups(A.pairs, A.slices, WAVES, A.num_groups)) return (int)hipErrorInvalidValue;
   const size_t lds = (size_t)WAVES * 2 * EPT * kWave * sizeof(float);
-  if (A.p_int == 2) {
-    hipLaunchKernelGGL((ssw_forward_grad_kv_kernel<EPT, WAVES, 2>), dim3((unsigned)groups), dim3(WAVES * 64), lds, stream, A);
-  } else {
-    hipLaunchKernelGGL((ssw_forward_grad_kv_kernel<EPT, WAVES, 0>), dim3((unsigned)groups), dim3(WAVES * 64), lds, stream, A);
-  }
+  const dim3 grid((unsigned)A.num_groups), block(WAVES * 64);
+  if (A.p_int == 2) hipLaunchKernelGGL((ssw_forward_grad_kv_kernel<EPT, WAVES, 2>), grid, block, lds, stream, A);
+  else hipLaunchKernelGGL((ssw_forward_grad_kv_kernel<EPT, WAVES, 0>), grid, block, lds, stream, A);
   return (int)hipGetLastError();
 }
 

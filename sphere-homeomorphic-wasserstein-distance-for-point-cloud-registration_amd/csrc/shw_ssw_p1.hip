@@ -194,83 +194,31 @@ __global__ __launch_bounds__(WAVES * 64) void ssw_level_median_kernel(SswArgs A,
   }
 }
 
-static int gcd_int(int a, int b) {
-  while (b) { const int t = a % b; a = b; b = t; }
-  return a;
-}
-
 template <int EPT, int WAVES>
-static int launch_level_median(SswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  const long groups = (total + WAVES - 1) / WAVES;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
-  const int g = gcd_int(A.n, A.m);
-  const int mg = A.m / g, ng = A.n / g;
-  const float inv_lcm = 1.f / ((float)A.n * (float)mg);
+static int launch_level_median_class(SswArgs& A, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, WAVES, A.num_groups)) return (int)hipErrorInvalidValue;
+  const LevelGrid L = level_grid(A.n, A.m);
   const bool grad = A.coef_s != nullptr;
   const size_t lds = (size_t)WAVES * (grad ? 4 : 2) * EPT * kWave * sizeof(float);
-  if (grad) {
-    hipLaunchKernelGGL((ssw_level_median_kernel<EPT, WAVES, true>), dim3((unsigned)groups), dim3(WAVES * 64), lds,
-                       stream, A, mg, ng, inv_lcm);
-  } else {
-    hipLaunchKernelGGL((ssw_level_median_kernel<EPT, WAVES, false>), dim3((unsigned)groups), dim3(WAVES * 64), lds,
-                       stream, A, mg, ng, inv_lcm);
-  }
+  const dim3 grid((unsigned)A.num_groups), block(WAVES * 64);
+  if (grad) hipLaunchKernelGGL((ssw_level_median_kernel<EPT, WAVES, true>), grid, block, lds, stream, A, L.mg, L.ng, L.inv_lcm);
+  else hipLaunchKernelGGL((ssw_level_median_kernel<EPT, WAVES, false>), grid, block, lds, stream, A, L.mg, L.ng, L.inv_lcm);
   return (int)hipGetLastError();
 }
 
-int dispatch_level_median_merge(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream);
-int dispatch_level_median_coop(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream);   // shw_ssw_p1_coop.hip
-bool level_median_coop_trains(int n, int m);
-int level_median_coop_slots(int total);
-
-// SHW_P1_SEARCH_KERNEL=1 (diagnostic): use the one-wave search kernel at every size
-static bool p1_search_kernel_forced() {
-  static const bool forced = [] { const char* e = getenv("SHW_P1_SEARCH_KERNEL"); return e && e[0] == '1'; }();
-  return forced;
-}
-
-// SHW_P1_KERNEL=coop | merge (diagnostic / A-B): the cooperative kernel of shw_ssw_p1_coop.hip, or the two-wave merge
-// kernel, wherever they can run
-static int p1_kernel_forced() {
-  static const int forced = [] { const char* e = getenv("SHW_P1_KERNEL"); return e ? (e[0] == 'c' ? 1 : (e[0] == 'm' ? 2 : 0)) : 0; }();
-  return forced;
-}
-
-int dispatch_level_median(SswArgs& A, hipStream_t stream) {
-  const bool small = A.n <= 2048 && A.m <= 2048;
-  const bool grad = A.coef_s != nullptr;
-  // cooperative kernel (one distribution sort of the tagged concatenation, shw_ssw_p1_coop.hip): every shape above 2048
-  // points; at or below, the loss from 1025 merged atoms on (measured at n = m = 2048 / 1024: 0.42 / 0.20 ms against the
-  // merge kernel's 0.54 / 0.25) -- training stays with the merge kernel there (0.97 / 0.42 against 0.94 / 0.45 ms)
-  // round 3: ... unless the cooperative kernel's class (20 / 24 / 32 merged atoms per lane) is smaller than the merge
-  // kernel's two power-of-two halves by more than the 12 % the merge kernel is faster per slot (n = m = 1200: 2560 against
-  // 4096 slots, 0.52 against 0.74 ms per step)
-  bool coop = small ? (A.n + A.m > 1024 && (!grad || 9 * level_median_coop_slots(A.n + A.m) < 8 * 128 * ept_for(A.n, A.m)))
-                    : (!grad || level_median_coop_trains(A.n, A.m));
-  if (p1_kernel_forced() == 1 && A.n + A.m > 1024) coop = true;
-  if (p1_kernel_forced() == 2 && small) coop = false;
-  if (p1_search_kernel_forced()) coop = false;
-  if (coop || (small && !p1_search_kernel_forced())) {
-    const int g = gcd_int(A.n, A.m);
-    const int mg = A.m / g, ng = A.n / g;
-    const float inv_lcm = 1.f / ((float)A.n * (float)mg);
-    // (merge kernel: two waves per slice, merge by the sorting network, shw_ssw_p1_merge.hip)
-    return coop ? dispatch_level_median_coop(A, mg, ng, inv_lcm, stream) : dispatch_level_median_merge(A, mg, ng, inv_lcm, stream);
-  }
-  switch (ept_for(A.n, A.m)) {
+int launch_level_median(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_level_median<SHW_DEV_ONLY_EPT, 1>(A, stream);
+    case SHW_DEV_ONLY_EPT: return launch_level_median_class<SHW_DEV_ONLY_EPT, 1>(A, stream);
 #else
-    case 1: return launch_level_median<1, 4>(A, stream);
-    case 2: return launch_level_median<2, 4>(A, stream);
-    case 4: return launch_level_median<4, 4>(A, stream);
-    case 8: return launch_level_median<8, 4>(A, stream);
-    case 16: return launch_level_median<16, 2>(A, stream);
-    case 32: return launch_level_median<32, 1>(A, stream);
-    case 64: return launch_level_median<64, 1>(A, stream);
-    case 128: return launch_level_median<128, 1>(A, stream);
+    case 1: return launch_level_median_class<1, 4>(A, stream);
+    case 2: return launch_level_median_class<2, 4>(A, stream);
+    case 4: return launch_level_median_class<4, 4>(A, stream);
+    case 8: return launch_level_median_class<8, 4>(A, stream);
+    case 16: return launch_level_median_class<16, 2>(A, stream);
+    case 32: return launch_level_median_class<32, 1>(A, stream);
+    case 64: return launch_level_median_class<64, 1>(A, stream);
+    case 128: return launch_level_median_class<128, 1>(A, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

@@ -234,57 +234,24 @@ __global__ __launch_bounds__(W * 64) void ssw_level_median_coop_kernel(SswArgs A
 }
 
 template <int EPT, int W, bool GRAD>
-static int launch_level_median_coop(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream) {
+static int launch_level_median_coop_class(SswArgs& A, hipStream_t stream) {
   typedef Coop<EPT, W, p1c_keys_per_bin<W, GRAD>()> C;
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
+  const LevelGrid L = level_grid(A.n, A.m);
   const size_t lds = (size_t)(C::LDS_FLOATS + (GRAD ? C::CAP : 0)) * sizeof(float);
-  auto kern = ssw_level_median_coop_kernel<EPT, W, GRAD>;
-  static bool raised[64] = {};          // once per instantiation and device (not inside a later stream capture)
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (lds > 64 * 1024 && !raised[dev & 63]) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)lds);
-    if (e != hipSuccess) return (int)e;
-    raised[dev & 63] = true;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(W * 64), lds, stream, A, mg, ng, inv_lcm);
+  constexpr auto kern = ssw_level_median_coop_kernel<EPT, W, GRAD>;
+  if (const hipError_t e = raise_dynamic_lds<kern>(lds)) return (int)e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)A.num_groups), dim3(W * 64), lds, stream, A, L.mg, L.ng, L.inv_lcm);
   return (int)hipGetLastError();
 }
 
-// training form available?  (12 bytes of LDS per merged slot up to n + m = 8192, 9 above: four keys per bin)
-bool level_median_coop_trains(int n, int m) { return next_pow2(n + m) <= 16384; }
-
-// p = 1 (called from dispatch_level_median, shw_ssw_p1.hip); coef_s != NULL: + coefficients.  W waves of 20 / 24 / 32 merged
-// atoms per lane: the smallest of the 12 classes (1280 ... 16384 slots) that holds n + m (round 3: 1200 + 1200 points
-// pay for 2560 slots, not 4096; SHW_KPL_CLASSES=0 keeps 32 per lane)
-static void level_median_coop_class(int total, int& W, int& ept) {
-  static const bool fine = [] { const char* v = getenv("SHW_KPL_CLASSES"); return !(v && v[0] == '0'); }();
-  W = 0; ept = 0;
-  for (int w = 1; w <= 8 && W == 0; w *= 2) {
-    for (int e : {20, 24, 32}) {
-      if ((e == 32 || fine) && 64 * w * e >= total) { W = w; ept = e; break; }
-    }
-  }
-}
-// merged slots of the class that serves n + m atoms (0: none)
-int level_median_coop_slots(int total) {
-  int W, ept;
-  level_median_coop_class(total, W, ept);
-  return 64 * W * ept;
-}
-
-int dispatch_level_median_coop(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream) {
+// p = 1, W waves of 20 / 24 / 32 merged atoms per lane (level_median_coop_class); coef_s != NULL: + coefficients
+int launch_level_median_coop(SswArgs& A, const Plan& P, hipStream_t stream) {
   const bool grad = A.coef_s != nullptr;
-  int W, ept;
-  level_median_coop_class(A.n + A.m, W, ept);
 #define SHW_P1C_CASE(WW, EE)                                                                        \
   case WW * 100 + EE:                                                                               \
-    return grad ? launch_level_median_coop<EE, WW, true>(A, mg, ng, inv_lcm, stream)                \
-                : launch_level_median_coop<EE, WW, false>(A, mg, ng, inv_lcm, stream)
-  switch (W * 100 + ept) {
+    return grad ? launch_level_median_coop_class<EE, WW, true>(A, stream) : launch_level_median_coop_class<EE, WW, false>(A, stream)
+  switch (P.waves * 100 + P.kpl) {
 #ifndef SHW_DEV_ONLY_EPT
     SHW_P1C_CASE(1, 20); SHW_P1C_CASE(1, 24); SHW_P1C_CASE(1, 32);
     SHW_P1C_CASE(2, 20); SHW_P1C_CASE(2, 24); SHW_P1C_CASE(2, 32);

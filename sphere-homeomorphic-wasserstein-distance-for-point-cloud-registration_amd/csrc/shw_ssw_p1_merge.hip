@@ -277,34 +277,32 @@ ssw_level_median_merge_kernel(SswArgs A, int mg, int ng, float inv_lcm) {
 }
 
 template <int EPT>
-static int launch_level_median_merge(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  if (total > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)total;
+static int launch_level_median_merge_class(SswArgs& A, hipStream_t stream) {
+  if (!problem_groups(A.pairs, A.slices, 1, A.num_groups)) return (int)hipErrorInvalidValue;
+  const LevelGrid L = level_grid(A.n, A.m);
+  const dim3 grid((unsigned)A.num_groups), block(128);
   if (A.coef_s != nullptr) {
     const size_t lds = (size_t)(EPT * 128 + 16) * sizeof(float) + (size_t)2 * EPT * kWave * sizeof(unsigned short);
-    hipLaunchKernelGGL((ssw_level_median_merge_kernel<EPT, true>), dim3((unsigned)total), dim3(128), lds, stream, A, mg,
-                       ng, inv_lcm);
+    hipLaunchKernelGGL((ssw_level_median_merge_kernel<EPT, true>), grid, block, lds, stream, A, L.mg, L.ng, L.inv_lcm);
   } else {
     const size_t lds = (size_t)(merge_loss_lds_floats<EPT>() + 16) * sizeof(float);
-    hipLaunchKernelGGL((ssw_level_median_merge_kernel<EPT, false>), dim3((unsigned)total), dim3(128), lds, stream, A,
-                       mg, ng, inv_lcm);
+    hipLaunchKernelGGL((ssw_level_median_merge_kernel<EPT, false>), grid, block, lds, stream, A, L.mg, L.ng, L.inv_lcm);
   }
   return (int)hipGetLastError();
 }
 
-// p = 1 for max(n, m) <= 2048, with or without coefficients (called from dispatch_level_median, shw_ssw_p1.hip)
-int dispatch_level_median_merge(SswArgs& A, int mg, int ng, float inv_lcm, hipStream_t stream) {
-  switch (ept_for(A.n, A.m)) {
+// p = 1 for max(n, m) <= 2048, with or without coefficients
+int launch_level_median_merge(SswArgs& A, const Plan& P, hipStream_t stream) {
+  switch (P.kpl) {
 #ifdef SHW_DEV_ONLY_EPT
-    case SHW_DEV_ONLY_EPT: return launch_level_median_merge<SHW_DEV_ONLY_EPT>(A, mg, ng, inv_lcm, stream);
+    case SHW_DEV_ONLY_EPT: return launch_level_median_merge_class<SHW_DEV_ONLY_EPT>(A, stream);
 #else
-    case 1: return launch_level_median_merge<1>(A, mg, ng, inv_lcm, stream);
-    case 2: return launch_level_median_merge<2>(A, mg, ng, inv_lcm, stream);
-    case 4: return launch_level_median_merge<4>(A, mg, ng, inv_lcm, stream);
-    case 8: return launch_level_median_merge<8>(A, mg, ng, inv_lcm, stream);
-    case 16: return launch_level_median_merge<16>(A, mg, ng, inv_lcm, stream);
-    case 32: return launch_level_median_merge<32>(A, mg, ng, inv_lcm, stream);
+    case 1: return launch_level_median_merge_class<1>(A, stream);
+    case 2: return launch_level_median_merge_class<2>(A, stream);
+    case 4: return launch_level_median_merge_class<4>(A, stream);
+    case 8: return launch_level_median_merge_class<8>(A, stream);
+    case 16: return launch_level_median_merge_class<16>(A, stream);
+    case 32: return launch_level_median_merge_class<32>(A, stream);
 #endif
     default: return (int)hipErrorInvalidValue;
   }

@@ -18,9 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <cstdlib>
-
 #include "../../include/shw.h"
+#include "dispatch.hpp"
 #include "wave_sort.hpp"
 
 #ifndef SHW_INC_MASK_BY_EXEC
@@ -37,7 +36,6 @@
 #endif
 
 namespace shw {
-
 
 struct SswArgs {
   const float* xs;
@@ -903,66 +901,5 @@ __device__ __forceinline__ float sorted_with_indices(const float* __restrict__ X
   unpack_sorted_words<EPT>(pk, orig, count, lane, val, idx);
   return part;
 }
-
-// ---------------------------------------------------------------------------------------------
-// host-side helpers shared by the per-kernel translation units
-// ---------------------------------------------------------------------------------------------
-inline int small_integer_power(float p) {
-  const int q = (int)p;
-  return ((float)q == p && q >= 1 && q <= 8) ? q : 0;
-}
-
-inline int next_pow2(int v) {
-  int r = 1;
-  while (r < v) r <<= 1;
-  return r;
-}
-
-
-// size class: registers per lane (EPT) for the padded point count
-inline int ept_for(int n, int m) {
-  const int padded = next_pow2(n > m ? n : m);
-  return padded <= 64 ? 1 : padded / 64;
-}
-
-// keys per lane of the two-wave kernels of 513..2048 points (round 3): the power-of-two classes plus 12, 20, 24 and 28, so
-// that a cloud pays for the next multiple of 256 points (768: of 256 x 3) and not for the next power of two -- the
-// notebooks' 1200 points (Flow_cube.ipynb:200) take 1280 slots instead of 2048.  SHW_KPL_CLASSES=0 keeps powers of two.
-inline int kpl_for(int n, int m, bool training = false) {
-  const int big = n > m ? n : m;
-  const int e = ept_for(n, m);
-  static const bool fine = [] { const char* v = getenv("SHW_KPL_CLASSES"); return !(v && v[0] == '0'); }();
-  if (!fine || e < 16) return e;
-  for (int k = e / 2 + 4; k < e; k += 4) {           // 16: 12;  32: 20, 24, 28
-    // (28 keys per lane: the loss kernel gains -- N = 1700: 0.299 -> 0.277 ms -- the training kernel does not: 0.632 -> 0.642)
-    if (k * 64 >= big && !(training && k == 28)) return k;
-  }
-  return e;
-}
-
-// keys per lane of the cooperative kernels above 2048 points (W = 2 or 4 waves per slice): 20, 24 or 32.  Measured per
-// pair at B N ~ 131 k, L = 512 (profiles/r03_size_sweep.txt): 28 keys per lane is never faster than 32 (the partially
-// filled 32 class costs the same), nor is 24 at W = 4 in training; 20 and 24 pay (N = 3000: training 1.40 -> 0.83 ms,
-// N = 5000: 1.88 -> 0.89).
-inline int coop_kpl_for(int points, int W, bool training) {
-  static const bool fine = [] { const char* v = getenv("SHW_KPL_CLASSES"); return !(v && v[0] == '0'); }();
-  if (!fine) return 32;
-  if (20 * 64 * W >= points) return 20;
-  if (24 * 64 * W >= points && !(training && W == 4)) return 24;
-  return 32;
-}
-
-// dispatchers, one per translation unit (SswArgs validated by the C entry points in shw_capi.hip)
-int dispatch_forward(SswArgs& A, hipStream_t stream);        // shw_ssw_fwd.hip   p != 1, loss only
-int dispatch_forward_grad(SswArgs& A, hipStream_t stream);   // shw_ssw_grad.hip  p != 1, loss + coefficients
-int dispatch_forward_grad2(SswArgs& A, hipStream_t stream);  // shw_ssw_grad2.hip two waves per slice, 257..2048 points
-int dispatch_forward_grad_coop(SswArgs& A, hipStream_t stream);   // shw_ssw_grad_coop.hip 2 / 4 waves per slice, 2049..8192 points
-int dispatch_level_median(SswArgs& A, hipStream_t stream);   // shw_ssw_p1.hip    p == 1 (coef_s != NULL: + coefficients)
-int dispatch_general(SswArgs& A, const float* wu, const float* wv, long wu_pair_stride, long wv_pair_stride,
-                     float* slice_theta, hipStream_t stream);   // shw_ssw_general.hip  p != 1, n != m / weights
-int launch_backward_points(const float* xs, const float* xt, const float* dirs, const float* coef_s,
-                           const float* coef_t, int pairs, int n, int m, int slices, long u_pair_stride,
-                           float scale, const float* pair_w, const float* total_w, float* grad_xs, float* grad_xt,
-                           hipStream_t stream);
 
 }  // namespace shw
