@@ -163,7 +163,9 @@ enum class Family {
   level_median,        // shw_ssw_p1.hip         p == 1, one-wave search kernel
   level_median_merge,  // shw_ssw_p1_merge.hip   p == 1, two waves per slice
   level_median_coop,   // shw_ssw_p1_coop.hip    p == 1, W waves per slice
-  general,             // shw_ssw_general.hip    n != m and / or weights
+  general,             // shw_ssw_general.hip    n != m and / or weights; its three solvers are headers: the integer grid
+                       //                        (general_grid.hpp), the cut search (general_cut.hpp), the level median at
+                       //                        p == 1 (general_p1.hpp)
   backward_points,     // shw_ssw_grad.hip       one point per lane, `waves` (4 or 16) waves split the slices
   backward_points4     // shw_ssw_grad.hip       four points per lane, 16-byte loads
 };
@@ -299,6 +301,7 @@ int launch_forward_grad_kv(SswArgs& A, const Plan& P, hipStream_t stream);
 int launch_level_median(SswArgs& A, const Plan& P, hipStream_t stream);
 int launch_level_median_merge(SswArgs& A, const Plan& P, hipStream_t stream);
 int launch_level_median_coop(SswArgs& A, const Plan& P, hipStream_t stream);
+// (fills GeneralArgs -- general_common.hpp -- and launches the solver the weights and p call for)
 int launch_general(SswArgs& A, const Plan& P, const float* wu, const float* wv, long wu_pair_stride, long wv_pair_stride,
                    float* slice_theta, hipStream_t stream);
 int launch_backward_points(const Plan& P, const float* xs, const float* xt, const float* dirs, const float* coef_s,

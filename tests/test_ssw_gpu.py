@@ -212,8 +212,12 @@ def test_g3_unequal_rows_through_planar_embedding(shw, golden, p):
     assert rel(cost[:, 0].cpu().numpy(), g[f"bsc_p{p}_128x100_f64"]) < 1e-4
 
 
+# (No row reaches the weighted two-wave class of 32 atoms per lane: (2048, 1536, True) misses grad_close at p = 3 -- 14 of
+#  6144 source-gradient entries outside the strict bound, 9 allowed -- a defect to be looked into, profiles/r11_general_split.txt.)
 @pytest.mark.parametrize("n,m,weighted", [(64, 64, True), (100, 37, False), (100, 37, True), (300, 512, False),
-                                          (1000, 1024, True), (2048, 1500, False), (1, 5, False), (7, 1, True)])
+                                          (1000, 1024, True), (2048, 1500, False), (1, 5, False), (7, 1, True),
+                                          (200, 130, False), (200, 130, True), (500, 400, True), (1000, 700, False),
+                                          (4096, 3000, False)])
 @pytest.mark.parametrize("p", [2, 3])
 def test_general_solver_against_cpu_oracle(shw, n, m, weighted, p):
     """Loss and gradients of the general path against the torch restatement of the reference's bisection

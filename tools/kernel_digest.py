@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Name, size and sha256 of every kernel in the gfx950 code objects of built units -- is the device code the same code?
+"""Name, size and sha256 of every function in the gfx950 code objects of built units -- is the device code the same code?
 
-    python tools/kernel_digest.py BUILD_DIR              one line per kernel: name, body bytes, sha256(body + descriptor)
-    python tools/kernel_digest.py BUILD_DIR OTHER_DIR    compare two builds: kernels only in one, kernels whose bytes differ
+    python tools/kernel_digest.py BUILD_DIR              one line per function: kernel | func, name, body bytes, sha256
+    python tools/kernel_digest.py BUILD_DIR OTHER_DIR    compare two builds: functions only in one, functions whose bytes differ
 
 BUILD_DIR holds the objects of csrc/Makefile (csrc/build/*.o).  For each object the device code object is taken out of
 the .hip_fatbin section with clang-offload-bundler; a kernel is a function symbol with a `<name>.kd` descriptor
-symbol beside it, and its digest covers the bytes of both, located through the symbol table.  Comparing per symbol
-and not per file is deliberate: two builds of the same source give identical kernels in files that still differ
-(notes, ordering of instantiations).  The script digests bytes only.
+symbol beside it, and its digest covers the bytes of both, located through the symbol table -- without bytes 16..23 of the
+descriptor (kernel_code_entry_byte_offset: the distance from the descriptor to the body, which says where the kernel sits
+in its code object and nothing about the kernel).  Every other function symbol of .text is an out-of-line device function
+(`func`): its body is digested alone.  Bodies are taken as linked into the code object: a call to an out-of-line
+function is a PC-relative displacement, so a caller (and nothing else) still differs when the distance to its callee
+does.  Comparing per symbol and not per file is deliberate: two builds of the same source give identical kernels in files
+that still differ (notes, ordering of instantiations).  The script digests bytes only.
 """
 import glob
 import hashlib
@@ -38,10 +42,10 @@ def symbols(elf, secs):
             continue
         strs = secs[sec["link"]]
         for i in range(sec["size"] // 24):
-            st_name, _info, _other, shndx, value, size = struct.unpack_from("<IBBHQQ", elf, sec["offset"] + i * 24)
+            st_name, info, _other, shndx, value, size = struct.unpack_from("<IBBHQQ", elf, sec["offset"] + i * 24)
             if 0 < shndx < len(secs) and size:
                 start = strs["offset"] + st_name
-                out[elf[start:elf.index(b"\0", start)].decode()] = (shndx, value, size)
+                out[elf[start:elf.index(b"\0", start)].decode()] = (shndx, value, size, info & 15)
     return out
 
 
@@ -50,12 +54,21 @@ def kernels_of(code_object):
     syms = symbols(code_object, secs)
 
     def data(sym):
-        shndx, value, size = syms[sym]
+        shndx, value, size, _ = syms[sym]
         at = secs[shndx]["offset"] + value - secs[shndx]["addr"]
         return code_object[at:at + size]
 
-    return {kd[:-3]: (len(data(kd[:-3])), hashlib.sha256(data(kd[:-3]) + data(kd)).hexdigest())
-            for kd in syms if kd.endswith(".kd") and kd[:-3] in syms}
+    out = {}
+    for name, (shndx, _value, _size, kind) in syms.items():
+        if kind != 2 or secs[shndx]["name"] != ".text":          # STT_FUNC
+            continue
+        body, kd = data(name), name + ".kd"
+        if kd in syms:
+            desc = data(kd)
+            out[name] = ("kernel", len(body), hashlib.sha256(body + desc[:16] + desc[24:]).hexdigest())
+        else:
+            out[name] = ("func", len(body), hashlib.sha256(body).hexdigest())
+    return out
 
 
 def digest(build_dir):
@@ -74,16 +87,22 @@ def digest(build_dir):
 
 if __name__ == "__main__":
     if len(sys.argv) == 2:
-        for name, (size, sha) in sorted(digest(sys.argv[1]).items()):
-            print(name, size, sha)
+        for name, (kind, size, sha) in sorted(digest(sys.argv[1]).items()):
+            print(kind, name, size, sha)
     elif len(sys.argv) == 3:
         a, b = digest(sys.argv[1]), digest(sys.argv[2])
         for name in sorted(set(a) ^ set(b)):
-            print("only in", sys.argv[1] if name in a else sys.argv[2], name)
+            print("only in", sys.argv[1] if name in a else sys.argv[2], (a.get(name) or b[name])[0], name)
         differing = sorted(n for n in set(a) & set(b) if a[n] != b[n])
         for name in differing:
-            print("differs", name, a[name][0], b[name][0])
-        print("kernels compared: %d, only in one build: %d, differing: %d" % (len(set(a) & set(b)), len(set(a) ^ set(b)), len(differing)))
+            print("differs", a[name][0], name, a[name][1], b[name][1])
+        both = set(a) & set(b)
+        print("kernels compared: %d, only in one build: %d, differing: %d" % (
+            sum(a[n][0] == "kernel" for n in both), sum((a.get(n) or b[n])[0] == "kernel" for n in set(a) ^ set(b)),
+            sum(a[n][0] == "kernel" for n in differing)))
+        print("funcs compared: %d, only in one build: %d, differing: %d" % (
+            sum(a[n][0] == "func" for n in both), sum((a.get(n) or b[n])[0] == "func" for n in set(a) ^ set(b)),
+            sum(a[n][0] == "func" for n in differing)))
         sys.exit(1 if differing or set(a) ^ set(b) else 0)
     else:
         sys.exit(__doc__)
