@@ -40,6 +40,11 @@
 // min(floor(key * NB), NB-1) by a saturating v_cvt, counters in keys, pads steered by selects -- because the new one
 // made their kernels slower (see below, "the classes with pads").
 //
+// The steps as functions: 1 binsort_histogram_full / binsort_histogram, which end in 2 binsort_scan; 3 binsort_place_full /
+// binsort_place; 4-5 binsort_read_back_and_fix (full classes: four phases per trip) and oddeven_fixup (classes with pads).
+// Shared by the sorts built on this one (bin_sort_idx.hpp, coop_sort.hpp, coop_sort_kv.hpp): wave_inclusive_scan_dpp and
+// wave_inclusive_max_dpp (step 2), binsort_boundary<KEYS> (step 5) and the address map binsort_addr.
+//
 // LDS per wave: NB counters (128*EPT bytes) + a 64*EPT-float staging buffer (256*EPT bytes).  LDS operations of one
 // wave execute in order and nothing here is shared with another wave: no barrier.
 #pragma once
@@ -61,28 +66,8 @@
 #define SHW_BINSORT_MAX_RUN 40
 #endif
 // the cooperative sorts (several waves per slice) finish a run that straddles two waves inside a 64-key window: < 32
-// 1: the counter offsets of the histogram pass are held in registers for the placement pass (an empty asm makes them
-// opaque: left alone the compiler recomputes the FMA and the AND per key there, 2 x 64 more VALU instructions per slice
-// and 34 fewer VGPRs); 0: the compiler chooses
-#ifndef SHW_BINSORT_KEEP_OFF
-#define SHW_BINSORT_KEEP_OFF 1
-#endif
-#if SHW_BINSORT_KEEP_OFF
-#define BINSORT_PIN_OFF(x) asm volatile("" : "+v"(x))
-#else
-#define BINSORT_PIN_OFF(x) ((void)0)
-#endif
 #ifndef SHW_COOP_MAX_RUN
 #define SHW_COOP_MAX_RUN 24
-#endif
-// The full classes' fix-up loop (binsort_read_back_and_fix).  1: four phases per trip and the last g mod 4 phases as
-// straight-line code behind wave-uniform branches; 0: the loop of two phases of round 7
-#ifndef SHW_BINSORT_FIX4
-#define SHW_BINSORT_FIX4 1
-#endif
-// 1: the exchange across the lane boundary by two DPP wave shifts (binsort_boundary_dpp); 0: two ds_bpermute and two selects
-#ifndef SHW_BINSORT_DPP_BOUNDARY
-#define SHW_BINSORT_DPP_BOUNDARY 1
 #endif
 
 namespace shw {
@@ -131,6 +116,44 @@ __device__ __forceinline__ int wave_inclusive_scan_dpp(int v) {
   t = __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false); v += t;            // row_bcast:31 -> rows 2, 3
   return v;
 }
+// inclusive prefix maximum of non-negative values by the same six steps: lane 63 ends up with the maximum of the wave
+__device__ __forceinline__ int wave_inclusive_max_dpp(int v) {
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
+  v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
+  return v;
+}
+
+// Step 2 of a one-wave sort: exclusive prefix sum over the 64 BPL counters, in place (lane owns counters
+// [lane*BPL, (lane+1)*BPL)).  Returns the largest counter (wave-uniform), in the counters' own unit.
+template <int BPL>
+__device__ __forceinline__ int binsort_scan(unsigned* cnt, int lane) {
+  unsigned c[BPL];
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + lane * BPL + j * 4);
+    c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
+  }
+  unsigned run = 0, total = 0;
+#pragma unroll
+  for (int j = 0; j < BPL; ++j) {
+    run = c[j] > run ? c[j] : run;
+    const unsigned t = c[j];
+    c[j] = total;                                        // exclusive inside the lane
+    total += t;
+  }
+  const int incl = wave_inclusive_scan_dpp((int)total);
+  const unsigned base = (unsigned)incl - total;
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j)
+    *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
+        u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
+  __builtin_amdgcn_wave_barrier();
+  return __builtin_amdgcn_readlane(wave_inclusive_max_dpp((int)run), 63);
+}
 
 // Byte offset of a key's counter: 4 * bin, bin in [0, NB), monotone non-decreasing in the key over [0, 1].
 //     off = bits(fma(key, 4 NB - 1, 2^23)) & (next_pow2(4 NB) - 4)
@@ -165,15 +188,36 @@ __device__ __forceinline__ bool binsort_keys_fit(const float (&key)[EPT]) {
   return __ballot(bad) == 0ull;
 }
 
-// one compare-exchange between the last key of every lane and the first key of the next lane
-template <int EPT>
-__device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
-  const float nxt = as_f(__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, as_i(x[0])));
-  const float prv = as_f(__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, as_i(x[EPT - 1])));
-  const float hi = __builtin_fminf(x[EPT - 1], lane < 63 ? nxt : __builtin_inff());
-  const float lo = __builtin_fmaxf(x[0], lane > 0 ? prv : -__builtin_inff());
-  x[EPT - 1] = hi;
-  x[0] = lo;
+// value of `x` held by lane `src` (ds_bpermute)
+__device__ __forceinline__ float from_lane(int src, float x) { return as_f(__builtin_amdgcn_ds_bpermute(src << 2, as_i(x))); }
+__device__ __forceinline__ unsigned from_lane(int src, unsigned x) { return (unsigned)__builtin_amdgcn_ds_bpermute(src << 2, (int)x); }
+
+// one compare-exchange between the last key of every lane and the first key of the next lane; the two ends of the wave
+// meet the highest / lowest key of the policy (KEYS::bound) and keep their own.  Needs EPT >= 2.
+template <class KEYS, int EPT>
+__device__ __forceinline__ void binsort_boundary(typename KEYS::type (&x)[EPT], int lane) {
+  const typename KEYS::type nxt = from_lane(min(lane + 1, 63), x[0]);
+  const typename KEYS::type prv = from_lane(max(lane - 1, 0), x[EPT - 1]);
+  x[EPT - 1] = KEYS::lo(x[EPT - 1], lane < 63 ? nxt : KEYS::bound(true));
+  x[0] = KEYS::hi(x[0], lane > 0 ? prv : KEYS::bound(false));
+}
+
+// g phases of odd-even transposition over the keys of a wave, two phases per loop trip (wave-uniform trip count): pairs
+// (2i, 2i+1) inside a lane; then pairs (2i+1, 2i+2) and the pair across every lane boundary.  The loop of the classes
+// with pads (binsort_place).  The full classes have their own, four phases per trip (binsort_read_back_and_fix).  The sort
+// with indices and the cooperative sorts write this same loop out in place around binsort_boundary: called as a function
+// it compiles to other code there (profiles/r12_sort_dedup.txt) -- a change to this loop goes to those three as well.
+template <class KEYS, int EPT>
+__device__ __forceinline__ void oddeven_fixup(typename KEYS::type (&key)[EPT], int lane, int g) {
+  for (int phase = 0; phase < g; phase += 2) {
+#pragma unroll
+    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<KEYS>(key[r], key[r + 1]);
+    if (phase + 1 < g) {
+#pragma unroll
+      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<KEYS>(key[r], key[r + 1]);
+      binsort_boundary<KEYS, EPT>(key, lane);
+    }
+  }
 }
 
 // Key policy of the fix-up phases of the FULL classes: the v_min_f32 / v_max_f32 of F32Keys and nothing else.  The
@@ -187,6 +231,8 @@ __device__ __forceinline__ void binsort_boundary(float (&x)[EPT], int lane) {
 // v_min / v_max itself, and rows with NaNs have no defined order.  Plain VALU: no wait states, nothing for s_waitcnt; not
 // volatile, so the compiler schedules and removes them like any other pure operation.
 // The classes with pads (binsort_place) and the cooperative sort (coop_sort.hpp) keep F32Keys: not measured with this.
+// (Round 7 exchanged the keys across the lane boundary with these two instructions behind two ds_bpermute and two
+// +-inf selects; round 8 replaced that by binsort_boundary_dpp.)
 struct F32KeysRaw {
   typedef float type;
   static __device__ __forceinline__ float lo(float a, float b) {
@@ -201,21 +247,11 @@ struct F32KeysRaw {
   }
 };
 
-// binsort_boundary with the compare-exchange of F32KeysRaw
-template <int EPT>
-__device__ __forceinline__ void binsort_boundary_raw(float (&x)[EPT], int lane) {
-  const float nxt = as_f(__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, as_i(x[0])));
-  const float prv = as_f(__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, as_i(x[EPT - 1])));
-  const float hi = F32KeysRaw::lo(x[EPT - 1], lane < 63 ? nxt : __builtin_inff());
-  const float lo = F32KeysRaw::hi(x[0], lane > 0 ? prv : -__builtin_inff());
-  x[EPT - 1] = hi;
-  x[0] = lo;
-}
-
-// binsort_boundary_raw without LDS traffic and without selects: the neighbour's key comes through a DPP wave shift.
+// binsort_boundary on F32KeysRaw without LDS traffic and without selects: the neighbour's key comes through a DPP wave
+// shift (two ds_bpermute and two selects otherwise).
 //   hi = v_min_f32_dpp(x[0] of lane + 1, x[EPT-1])   wave_shl:1     lo = v_max_f32_dpp(x[EPT-1] of lane - 1, x[0])   wave_shr:1
 // No bound_ctrl: a lane without a source (63 for the first, 0 for the second) is switched off for that instruction and
-// keeps its destination, which holds its own key on entry ("+" operands) -- what the +-inf selects of the other form
+// keeps its destination, which holds its own key on entry ("+" operands) -- what the +-inf selects of binsort_boundary
 // give.  Both instructions read the keys as they stand after the odd phase: the destinations are early-clobber copies,
 // never the registers of x[0] / x[EPT-1] themselves.  A DPP operand written by the VALU instruction just before needs two
 // wait states, which the compiler cannot see into an asm block to provide: the s_nop 1 does.  Not volatile, plain "v"
@@ -240,14 +276,10 @@ __device__ __forceinline__ void binsort_even_phase(float (&key)[EPT]) {
   for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
 }
 template <int EPT>
-__device__ __forceinline__ void binsort_odd_phase(float (&key)[EPT], int lane) {
+__device__ __forceinline__ void binsort_odd_phase(float (&key)[EPT]) {
 #pragma unroll
   for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32KeysRaw>(key[r], key[r + 1]);
-#if SHW_BINSORT_DPP_BOUNDARY
   binsort_boundary_dpp<EPT>(key);
-#else
-  binsort_boundary_raw<EPT>(key, lane);
-#endif
 }
 
 // Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition
@@ -261,32 +293,26 @@ __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int
     key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
   }
   // odd-even transposition, g phases: even, odd, even, ... (wave-uniform trip count)
-#if SHW_BINSORT_FIX4
   // Four phases per trip: a compare-exchange needs a temporary, so the keys leave a phase one register over; after two
   // phases the compiler copies them back at the loop's back edge (31 v_mov per trip), after four it finds an assignment
   // that needs no copy.  The last g mod 4 phases are straight-line code behind wave-uniform branches: the keys of paths of
   // different length meet in different registers, which costs 16 v_mov_b64 at the loop's exit, 16 more for a remainder
-  // of two phases and 32 more for one of three -- once per sort, where the loop of two phases paid 31 v_mov per trip.
+  // of two phases and 32 more for one of three -- once per sort, where the loop of two phases (round 7) paid 31 v_mov per
+  // trip.
   int phase = 0;
   for (; phase + 4 <= g; phase += 4) {
     binsort_even_phase<EPT>(key);
-    binsort_odd_phase<EPT>(key, lane);
+    binsort_odd_phase<EPT>(key);
     binsort_even_phase<EPT>(key);
-    binsort_odd_phase<EPT>(key, lane);
+    binsort_odd_phase<EPT>(key);
   }
   if (phase < g) {
     binsort_even_phase<EPT>(key);
     if (phase + 1 < g) {
-      binsort_odd_phase<EPT>(key, lane);
+      binsort_odd_phase<EPT>(key);
       if (phase + 2 < g) binsort_even_phase<EPT>(key);
     }
   }
-#else
-  for (int phase = 0; phase < g; phase += 2) {
-    binsort_even_phase<EPT>(key);
-    if (phase + 1 < g) binsort_odd_phase<EPT>(key, lane);
-  }
-#endif
   __builtin_amdgcn_wave_barrier();
 }
 
@@ -312,43 +338,15 @@ __device__ __forceinline__ int binsort_histogram_full(const float (&key)[EPT], i
 #pragma unroll
     for (int j = 0; j < CH; ++j) {                       // result unused: ds_add_u32, nothing to wait for
       slot[r0 + j] = cb + binsort_off<NB>(key[r0 + j]);
-      BINSORT_PIN_OFF(slot[r0 + j]);
+      // held in a register for the placement pass: the empty asm makes the offset opaque.  Left alone the compiler
+      // recomputes the FMA and the AND per key there (2 x 64 more VALU instructions per slice, 34 fewer VGPRs)
+      asm volatile("" : "+v"(slot[r0 + j]));
       __hip_atomic_fetch_add(lds_counter(slot[r0 + j]), 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();
-  // scan: lane owns bins [lane*BPL, (lane+1)*BPL)
-  unsigned c[BPL];
-#pragma unroll
-  for (int j = 0; j < BPL / 4; ++j) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + lane * BPL + j * 4);
-    c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
-  }
-  unsigned run = 0, total = 0;
-#pragma unroll
-  for (int j = 0; j < BPL; ++j) {
-    run = c[j] > run ? c[j] : run;
-    const unsigned t = c[j];
-    c[j] = total;                                        // exclusive inside the lane
-    total += t;
-  }
-  const int incl = wave_inclusive_scan_dpp((int)total);
-  const unsigned base = (unsigned)incl - total;
-#pragma unroll
-  for (int j = 0; j < BPL / 4; ++j)
-    *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
-        u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
-  __builtin_amdgcn_wave_barrier();
-  // wave maximum of the run lengths (counted in bytes: four per key)
-  int g = (int)run;
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x111, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x112, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x114, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x118, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x142, 0xa, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x143, 0xc, 0xf, false));
-  return __builtin_amdgcn_readlane(g, 63) >> 2;
+  return binsort_scan<BPL>(cnt, lane) >> 2;              // the largest counter, counted in bytes: four per key
 }
 
 // Steps 3-5 of a full class (only after binsort_histogram_full returned g <= SHW_BINSORT_MAX_RUN).  The byte position of
@@ -432,37 +430,7 @@ __device__ __forceinline__ int binsort_histogram(const float (&key)[EPT], int la
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();
-  // scan: lane owns bins [lane*BPL, (lane+1)*BPL)
-  unsigned c[BPL];
-#pragma unroll
-  for (int j = 0; j < BPL / 4; ++j) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + lane * BPL + j * 4);
-    c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
-  }
-  unsigned run = 0, total = 0;
-#pragma unroll
-  for (int j = 0; j < BPL; ++j) {
-    run = c[j] > run ? c[j] : run;
-    const unsigned t = c[j];
-    c[j] = total;                                        // exclusive inside the lane
-    total += t;
-  }
-  const int incl = wave_inclusive_scan_dpp((int)total);
-  const unsigned base = (unsigned)incl - total;
-#pragma unroll
-  for (int j = 0; j < BPL / 4; ++j)
-    *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
-        u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
-  __builtin_amdgcn_wave_barrier();
-  // wave maximum of the run lengths
-  int g = (int)run;
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x111, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x112, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x114, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x118, 0xf, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x142, 0xa, 0xf, false));
-  g = max(g, __builtin_amdgcn_update_dpp(0, g, 0x143, 0xc, 0xf, false));
-  return __builtin_amdgcn_readlane(g, 63);
+  return binsort_scan<BPL>(cnt, lane);
 }
 
 // Steps 3-5 (only after binsort_histogram returned g <= SHW_BINSORT_MAX_RUN).  The position of a live key is what
@@ -514,16 +482,7 @@ __device__ __forceinline__ void binsort_place(float (&key)[EPT], int lane, int n
     const f32x4 v = *reinterpret_cast<const f32x4*>(bytes + binsort_addr<EPT>(pos0));
     key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
   }
-  // odd-even transposition, g phases (wave-uniform trip count)
-  for (int phase = 0; phase < g; phase += 2) {
-#pragma unroll
-    for (int r = 0; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
-    if (phase + 1 < g) {
-#pragma unroll
-      for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
-      binsort_boundary<EPT>(key, lane);
-    }
-  }
+  oddeven_fixup<F32Keys, EPT>(key, lane, g);
   __builtin_amdgcn_wave_barrier();
 }
 

@@ -7,6 +7,10 @@
 // exact coordinates by ORIGINAL index (they wait in registers while the words travel), and unpack_sorted_words
 // gathers them and repairs the few pairs whose quantised coordinates collide -- the result is the stable ascending
 // order torch.sort gives the reference (:163-164).
+// From bin_sort.hpp: wave_inclusive_scan_dpp, wave_inclusive_max_dpp, binsort_boundary<U32Keys>, binsort_addr.  The scan
+// and the fix-up loop are written out here and not calls of binsort_scan / oddeven_fixup: this file reduces the maximum
+// before the barrier, not after, and either call compiles to other code in the training kernels
+// (profiles/r12_sort_dedup.txt).
 // LDS per wave: 32*EPT counters + 64*EPT words; nothing is needed beside them (the network version keeps a
 // 64*EPT-float row of coordinates by original index: the same 4 bytes per atom).
 #pragma once
@@ -19,16 +23,6 @@ namespace shw {
 // slot of a lane for the power-of-two classes, the next power of two above that otherwise (1024 for 20 .. 28 keys per lane)
 template <int EPT>
 constexpr int binsort_idx_bins() { return next_pow2_c(SHW_BINSORT_NB_PER_EPT * EPT); }
-
-template <int EPT>
-__device__ __forceinline__ void binsort_boundary_u32(unsigned (&x)[EPT], int lane) {
-  const unsigned nxt = (unsigned)__builtin_amdgcn_ds_bpermute(min(lane + 1, 63) << 2, (int)x[0]);
-  const unsigned prv = (unsigned)__builtin_amdgcn_ds_bpermute(max(lane - 1, 0) << 2, (int)x[EPT - 1]);
-  const unsigned up = lane < 63 ? nxt : 0xffffffffu;
-  const unsigned dn = lane > 0 ? prv : 0u;
-  x[EPT - 1] = x[EPT - 1] < up ? x[EPT - 1] : up;
-  x[0] = x[0] > dn ? x[0] : dn;
-}
 
 // project one cloud, sort it with its permutation; returns the coordinate sum of the lane.
 //   cnt : binsort_idx_bins<EPT>() counters (32*EPT for the power-of-two classes), buf : 64*EPT words (scatter target, then coordinates by original index -- still holding
@@ -81,7 +75,7 @@ __device__ __forceinline__ float sorted_with_indices_binned(const float* __restr
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();
-  // ---- scan (as binsort_histogram)
+  // ---- scan (binsort_scan of bin_sort.hpp, with the maximum in front of the barrier)
   int g;
   {
     unsigned c[BPL];
@@ -104,14 +98,7 @@ __device__ __forceinline__ float sorted_with_indices_binned(const float* __restr
     for (int j = 0; j < BPL / 4; ++j)
       *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
           u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
-    int gw = (int)run;
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x111, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x112, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x114, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x118, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x142, 0xa, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x143, 0xc, 0xf, false));
-    g = __builtin_amdgcn_readlane(gw, 63);
+    g = __builtin_amdgcn_readlane(wave_inclusive_max_dpp((int)run), 63);
   }
   __builtin_amdgcn_wave_barrier();
   char* bytes = reinterpret_cast<char*>(buf);
@@ -148,7 +135,7 @@ __device__ __forceinline__ float sorted_with_indices_binned(const float* __restr
       if (phase + 1 < g) {
 #pragma unroll
         for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<U32Keys>(pk[r], pk[r + 1]);
-        binsort_boundary_u32<EPT>(pk, lane);
+        binsort_boundary<U32Keys, EPT>(pk, lane);
       }
     }
   } else {

@@ -11,7 +11,11 @@
 //     waves is finished by a 64-key window sort around the seam (one key per lane, the cross-lane network of
 //     wave_sort.hpp): runs are at most SHW_COOP_MAX_RUN (< 32) long, so the window holds them whole;
 //   * workgroup barriers separate the steps (7 per sort).
-// Data with longer runs falls back to the bitonic network (in-wave sort + merge across waves through LDS).
+// Data with longer runs falls back to the bitonic network (in-wave sort + merge across waves through LDS: coop_bitonic,
+// which is also the sort of the multi-wave loss kernel of shw_ssw_fwd.hip).
+// From bin_sort.hpp: wave_inclusive_scan_dpp, wave_inclusive_max_dpp, binsort_boundary<F32Keys>, binsort_addr.  The in-lane
+// part of the scan, the read-back and the fix-up loop are written out in coop_sort: as calls they compile to other code
+// (profiles/r12_sort_dedup.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,33 +53,40 @@ __device__ __forceinline__ unsigned coop_addr(unsigned pos) {
   else return (pos << 2) ^ ((pos >> 3) & 0x10u);             // EPT = 4: one chunk per lane, rows of 8 lanes
 }
 
-// ---- cross-wave bitonic merge (fallback path; generalises the multi-wave loss kernel's merge to any EPT) -------
-template <int EPT, int W>
-__device__ __forceinline__ void coop_exchange(float (&key)[EPT], float* buf, int wave, int lane, int partner,
-                                              bool mirror, bool upper) {
+// ---- bitonic sort by the W waves of a workgroup: the fallback of the cooperative sorts and the whole sort of the
+// multi-wave loss kernel (shw_ssw_fwd.hip).  KEYS is the key policy (wave_sort.hpp): F32Keys, or U64Items for the items
+// of coop_sort_kv.hpp.  Each wave sorts its 64*EPT keys in registers; the chunks are merged by the remaining levels of the
+// same network, whose first stages pair keys of DIFFERENT waves: those go through one LDS exchange each (write EPT
+// registers, barrier, read the partner wave's slot, barrier), and because the lower / upper role of such a stage is the
+// same for a whole wave it is a plain KEYS::lo / KEYS::hi.  buf: EPT * 64 W keys.
+template <int EPT, int W, class KEYS>
+__device__ __forceinline__ void coop_exchange(typename KEYS::type (&key)[EPT], typename KEYS::type* buf, int wave,
+                                              int lane, int partner, bool mirror, bool upper) {
   constexpr int NCOL = 64 * W;
 #pragma unroll
   for (int r = 0; r < EPT; ++r) buf[r * NCOL + wave * 64 + lane] = key[r];
   __syncthreads();
 #pragma unroll
   for (int r = 0; r < EPT; ++r) {
-    const float p = mirror ? buf[(EPT - 1 - r) * NCOL + partner * 64 + (63 - lane)] : buf[r * NCOL + partner * 64 + lane];
-    key[r] = upper ? __builtin_fmaxf(key[r], p) : __builtin_fminf(key[r], p);
+    const typename KEYS::type p =
+        mirror ? buf[(EPT - 1 - r) * NCOL + partner * 64 + (63 - lane)] : buf[r * NCOL + partner * 64 + lane];
+    key[r] = upper ? KEYS::hi(key[r], p) : KEYS::lo(key[r], p);
   }
   __syncthreads();
 }
 
-template <int EPT, int W>
-__device__ __forceinline__ void coop_bitonic(float (&key)[EPT], float* buf, int wave, int lane) {
-  wave_sort<EPT>(key, lane);
+template <int EPT, int W, class KEYS = F32Keys>
+__device__ __forceinline__ void coop_bitonic(typename KEYS::type (&key)[EPT], typename KEYS::type* buf, int wave, int lane) {
+  if constexpr (sizeof(typename KEYS::type) == sizeof(item_t)) wave_sort_kv<EPT>(key, lane);
+  else wave_sort<EPT>(key, lane);
 #pragma unroll
   for (int c = 1; (1 << c) <= W; ++c) {                       // merge blocks of 2^c waves
-    coop_exchange<EPT, W>(key, buf, wave, lane, wave ^ ((1 << c) - 1), true, (wave & (1 << (c - 1))) != 0);
+    coop_exchange<EPT, W, KEYS>(key, buf, wave, lane, wave ^ ((1 << c) - 1), true, (wave & (1 << (c - 1))) != 0);
 #pragma unroll
     for (int t = c - 2; t >= 0; --t)
-      coop_exchange<EPT, W>(key, buf, wave, lane, wave ^ (1 << t), false, (wave & (1 << t)) != 0);
-    xlane_stages<F32Keys, EPT, 32>(key, lane);
-    lane_stages<F32Keys, EPT, EPT / 2>(key);
+      coop_exchange<EPT, W, KEYS>(key, buf, wave, lane, wave ^ (1 << t), false, (wave & (1 << t)) != 0);
+    xlane_stages<KEYS, EPT, 32>(key, lane);
+    lane_stages<KEYS, EPT, EPT / 2>(key);
   }
 }
 
@@ -159,13 +170,7 @@ __device__ __forceinline__ void coop_sort(float (&key)[EPT], int wave, int lane,
     total += t;
   }
   const int incl = wave_inclusive_scan_dpp((int)total);
-  int gw = (int)run;
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x111, 0xf, 0xf, false));
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x112, 0xf, 0xf, false));
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x114, 0xf, 0xf, false));
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x118, 0xf, 0xf, false));
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x142, 0xa, 0xf, false));
-  gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x143, 0xc, 0xf, false));
+  const int gw = wave_inclusive_max_dpp((int)run);
   if (lane == 63) { red[wave] = incl; red[W + wave] = gw; }
   __syncthreads();
   int base = 0, g = 0;
@@ -229,7 +234,7 @@ __device__ __forceinline__ void coop_sort(float (&key)[EPT], int wave, int lane,
     if (phase + 1 < g) {
 #pragma unroll
       for (int r = 1; r + 1 < EPT; r += 2) cmp_swap<F32Keys>(key[r], key[r + 1]);
-      binsort_boundary<EPT>(key, lane);
+      binsort_boundary<F32Keys, EPT>(key, lane);
     }
   }
   // ---- 6. seams between waves ----------------------------------------------------------------------------------

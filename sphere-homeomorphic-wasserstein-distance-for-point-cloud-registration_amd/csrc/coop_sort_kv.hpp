@@ -11,41 +11,19 @@
 // Same steps and layout as coop_sort: lane gl = wave*64 + lane owns points r*64W + gl on entry and sorted positions
 // gl*EPT + r on return; an item at position p sits at the 8 bytes of 4-byte slots 2p, 2p+1 of coop_addr<2 EPT>
 // (the same XOR permutation of 16-byte chunks: a ds_read_b128 returns two items).
+//
+// Shared with coop_sort.hpp: Coop, coop_addr, coop_zero_counters, lds_bitonic_sort and coop_bitonic<EPT, W, U64Items> (the
+// fallback network is one template over the key policy); from bin_sort.hpp wave_inclusive_scan_dpp and
+// wave_inclusive_max_dpp.  Deliberately NOT shared, because each changed the bytes of at least one kernel
+// (profiles/r12_sort_dedup.txt): the body of coop_sort_kv itself (steps 1-6 repeat coop_sort with item_key(it) for the
+// key, 8-byte slots at coop_addr<2 EPT>(2 pos) and two items per ds_read_b128), its fix-up loop, and
+// binsort_boundary_kv.  A fix in one of the two cooperative sorts belongs in the other too.
 #pragma once
 #include "coop_sort.hpp"
 
 namespace shw {
 
-// ---- cross-wave bitonic merge on items (fallback path) ---------------------------------------------------------
-template <int EPT, int W>
-__device__ __forceinline__ void coop_exchange_kv(item_t (&it)[EPT], item_t* buf, int wave, int lane, int partner,
-                                                 bool mirror, bool upper) {
-  constexpr int NCOL = 64 * W;
-#pragma unroll
-  for (int r = 0; r < EPT; ++r) buf[r * NCOL + wave * 64 + lane] = it[r];
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < EPT; ++r) {
-    const item_t p = mirror ? buf[(EPT - 1 - r) * NCOL + partner * 64 + (63 - lane)] : buf[r * NCOL + partner * 64 + lane];
-    it[r] = upper ? U64Items::hi(it[r], p) : U64Items::lo(it[r], p);
-  }
-  __syncthreads();
-}
-
-template <int EPT, int W>
-__device__ __forceinline__ void coop_bitonic_kv(item_t (&it)[EPT], item_t* buf, int wave, int lane) {
-  wave_sort_kv<EPT>(it, lane);
-#pragma unroll
-  for (int c = 1; (1 << c) <= W; ++c) {                       // merge blocks of 2^c waves
-    coop_exchange_kv<EPT, W>(it, buf, wave, lane, wave ^ ((1 << c) - 1), true, (wave & (1 << (c - 1))) != 0);
-#pragma unroll
-    for (int t = c - 2; t >= 0; --t)
-      coop_exchange_kv<EPT, W>(it, buf, wave, lane, wave ^ (1 << t), false, (wave & (1 << t)) != 0);
-    xlane_stages<U64Items, EPT, 32>(it, lane);
-    lane_stages<U64Items, EPT, EPT / 2>(it);
-  }
-}
-
+// binsort_boundary (bin_sort.hpp) for items: each neighbour's item crosses as two words
 template <int EPT>
 __device__ __forceinline__ void binsort_boundary_kv(item_t (&x)[EPT], int lane) {
   const unsigned a_lo = (unsigned)x[0], a_hi = (unsigned)(x[0] >> 32);
@@ -106,13 +84,7 @@ __device__ __forceinline__ void coop_sort_kv(item_t (&it)[EPT], int wave, int la
       total += t;
     }
     const int incl = wave_inclusive_scan_dpp((int)total);
-    int gw = (int)run;
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x111, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x112, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x114, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x118, 0xf, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x142, 0xa, 0xf, false));
-    gw = max(gw, __builtin_amdgcn_update_dpp(0, gw, 0x143, 0xc, 0xf, false));
+    const int gw = wave_inclusive_max_dpp((int)run);
     if (lane == 63) { red[wave] = incl; red[W + wave] = gw; }
     __syncthreads();
     int base = 0;
@@ -134,7 +106,7 @@ __device__ __forceinline__ void coop_sort_kv(item_t (&it)[EPT], int wave, int la
     // long runs (clustered data, duplicates): the network sorts it; counters re-zeroed for the next sort
     coop_zero_counters<EPT, W, KPB>(cnt, gl);
     if constexpr (is_pow2(EPT)) {
-      coop_bitonic_kv<EPT, W>(it, buf, wave, lane);
+      coop_bitonic<EPT, W, U64Items>(it, buf, wave, lane);
     } else {                                                 // (see lds_bitonic_sort; items are unique: plain <)
 #pragma unroll
       for (int r = 0; r < EPT; ++r) buf[r * C::NCOL + gl] = it[r];

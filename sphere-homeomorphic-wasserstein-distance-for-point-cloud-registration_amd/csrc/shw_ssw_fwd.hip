@@ -1,6 +1,6 @@
 // shw_ssw_fwd.hip -- loss-only kernel for p != 1 (key-only register sort).  See ssw_common.hpp.
 #include "ssw_common.hpp"
-#include "bin_sort.hpp"
+#include "coop_sort.hpp"
 
 #ifndef SHW_BINSORT
 #define SHW_BINSORT 1      // 1: distribution sort through LDS (bin_sort.hpp) for >= 8 keys per lane; 0: bitonic network only
@@ -133,7 +133,8 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 // ---------------------------------------------------------------------------------------------
 // Multi-wave form for 2048 < n <= 8192: W = 2 or 4 wavefronts of one workgroup share a slice.  Each wave
 // sorts its chunk of 2048 keys in registers exactly as above; the chunks are then merged by the remaining
-// levels of the same bitonic network, whose first stages pair elements of DIFFERENT waves: those go through
+// levels of the same bitonic network (coop_bitonic of coop_sort.hpp, the fallback of the cooperative sorts), whose
+// first stages pair elements of DIFFERENT waves: those go through
 // one LDS exchange each (write 32 registers, barrier, read the partner wave's slot, barrier), and because the
 // "lower / upper" role of such a stage is the same for a whole wave they are plain v_min / v_max.  The stages
 // below the wave level are the single-wave code (xlane_stages, lane_stages).  The source is sorted first and
@@ -143,34 +144,6 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 // 2048 source atoms; the three partial sums are added across waves in wave order through LDS, so all waves
 // take identical decisions.
 // ---------------------------------------------------------------------------------------------
-template <int W>
-__device__ __forceinline__ void cross_wave_exchange(float (&key)[32], float* buf, int wave, int lane, int partner,
-                                                    bool mirror, bool upper) {
-  constexpr int NCOL = 64 * W;
-#pragma unroll
-  for (int r = 0; r < 32; ++r) buf[r * NCOL + wave * 64 + lane] = key[r];
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 32; ++r) {
-    const float p = mirror ? buf[(31 - r) * NCOL + partner * 64 + (63 - lane)] : buf[r * NCOL + partner * 64 + lane];
-    key[r] = upper ? __builtin_fmaxf(key[r], p) : __builtin_fminf(key[r], p);
-  }
-  __syncthreads();
-}
-
-template <int W>
-__device__ __forceinline__ void merge_across_waves(float (&key)[32], float* buf, int wave, int lane) {
-#pragma unroll
-  for (int c = 1; (1 << c) <= W; ++c) {                       // merge blocks of 2^c waves
-    cross_wave_exchange<W>(key, buf, wave, lane, wave ^ ((1 << c) - 1), true, (wave & (1 << (c - 1))) != 0);
-#pragma unroll
-    for (int t = c - 2; t >= 0; --t)
-      cross_wave_exchange<W>(key, buf, wave, lane, wave ^ (1 << t), false, (wave & (1 << t)) != 0);
-    xlane_stages<F32Keys, 32, 32>(key, lane);
-    lane_stages<F32Keys, 32, 16>(key);
-  }
-}
-
 template <int W, int PMODE, bool FULL>
 __global__ __launch_bounds__(W * 64, 4) void ssw_forward_mw_kernel(SswArgs A) {
   constexpr int EPT = 32, NCOL = 64 * W, CHUNK = EPT * kWave;
@@ -196,8 +169,7 @@ __global__ __launch_bounds__(W * 64, 4) void ssw_forward_mw_kernel(SswArgs A) {
     int ln = lane;
     asm volatile("" : "+v"(ln));
     const float part = load_coords<EPT, FULL>(X + (long)base * A.pstride, n - base, ln, U, key, chunk_live);
-    wave_sort<EPT>(key, ln);
-    merge_across_waves<W>(key, buf, wave, ln);
+    coop_bitonic<EPT, W>(key, buf, wave, ln);
     if (which == 0) {
       part_u = wave_sum_uniform(part, lane);
 #pragma unroll
