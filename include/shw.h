@@ -16,7 +16,8 @@
  *   - clouds are fp32 row-major (pairs, points, 3); directions are fp32 (slices, 3, 2) orthonormal
  *     2-frames, either one set per pair (u_pair_stride = slices*6) or shared (u_pair_stride = 0).
  *   - the entries whose names end in _f64 take the same arrays as `double` (equal cloud sizes, uniform weights, at
- *     most SHW_MAX_POINTS_F64 points per cloud); every other entry is fp32.
+ *     most SHW_MAX_POINTS_F64 points per cloud; the *_general_f64 entries: any two sizes and weights, at most
+ *     SHW_MAX_POINTS_F64_GENERAL points per cloud); every other entry is fp32.
  */
 #ifndef SHW_H
 #define SHW_H
@@ -35,6 +36,7 @@ extern "C" {
                              shw_sinkhorn_forward_train takes plan / cost_matrix */
 #define SHW_MAX_POINTS 8192 /* per cloud, per pair */
 #define SHW_MAX_POINTS_F64 4096 /* per cloud, per pair, on the float64 entry points (shw_*_f64) */
+#define SHW_MAX_POINTS_F64_GENERAL 2048 /* per cloud, per pair, on the general float64 entry points (shw_*_general_f64) */
 
 /* ABI version of the loaded library (== SHW_ABI_VERSION of the header it was built from). */
 SHW_API int shw_abi_version(void);
@@ -160,7 +162,7 @@ SHW_API int shw_circle_ot(const float* u, const float* v, const float* wu, const
  * that call: the conventions of the header comment with `double` in place of fp32, kernels of their own
  * (csrc/shw_ssw_f64.hip: one workgroup per (pair, slice), double atan2, every sum in a fixed order -- results are
  * bit-identical from run to run).  n == m is required and 1 <= n <= SHW_MAX_POINTS_F64; anything else returns 1.
- * Weighted and unequal-size clouds stay on the fp32 entry points.
+ * Weighted and unequal-size clouds: the *_general_f64 entries further down, or the fp32 entry points.
  */
 
 /* Largest point count per cloud the float64 entry points accept (SHW_MAX_POINTS_F64). */
@@ -200,6 +202,50 @@ SHW_API int shw_ssw_reduce_f64(const double* slice_cost, int pairs, int slices, 
  *   grad_u, grad_v (rows*n) out, both NULL for a value-only call. */
 SHW_API int shw_circle_ot_f64(const double* u, const double* v, int rows, int n, int m, double p, int method,
                               double* cost, int32_t* aux, double* grad_u, double* grad_v, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Float64 general circular OT: weighted and / or unequal-size clouds, any p >= 1 (additive to ABI 3).
+ * The double form of shw_ssw_forward_general / shw_circle_ot for the shapes the entries above refuse: kernels of
+ * csrc/shw_ssw_f64_general.hip, one workgroup per (pair, slice), every sum in a fixed order -- results are bit-identical
+ * from run to run.  1 <= n, m <= SHW_MAX_POINTS_F64_GENERAL; anything else returns 1 without touching the device.
+ * p != 1 (and SHW_CIRCLE_BISECTION at every p) is the DEFINITION min over the cut theta in [-1, 1] of Cost(theta)
+ * (Cost: max_spherical_sliced_w.py:68-113), found exactly -- Cost is convex and piecewise linear in theta -- and not
+ * the reference's stopping rule (:191-200), which ends up to 1.6e-11 above it (fixture G14).
+ */
+
+/* Largest point count per cloud the general float64 entry points accept (SHW_MAX_POINTS_F64_GENERAL). */
+SHW_API int shw_max_points_f64_general(void);
+
+/* Replaces: sliced_cost on double tensors with n != m and / or weights, up to the mean over slices
+ * (max_spherical_sliced_w.py:251-286, _fast.py:258-295: sort :262-269, cumsum of the gathered weights :161-167,
+ * binary_search_circle :117-207 with dCost :25-65 and Cost :68-113 for p != 1, emd1D_circle :210-247 for p == 1).
+ * Arguments as shw_ssw_forward_general, in double:
+ *   wu (n) or (pairs, n), wv (m) or (pairs, m): weights summing to 1, NULL = uniform; w*_pair_stride = 0 for a shared
+ *   row, else the doubles between consecutive pairs' rows;
+ *   slice_cost (pairs*slices) out; slice_theta (pairs*slices) out, may be NULL: the cut theta* (p != 1) or the median
+ *   level (p == 1);
+ *   coef_s (pairs*slices*n), coef_t (pairs*slices*m) double scratch, both NULL for a loss-only call: d cost(b,l) / d coord
+ *   at the detached cut (:207) in ORIGINAL point order, the input of shw_ssw_backward_points_general_f64. */
+SHW_API int shw_ssw_forward_general_f64(const double* xs, const double* xt, const double* dirs, const double* wu,
+                                        const double* wv, long wu_pair_stride, long wv_pair_stride, int pairs, int n,
+                                        int m, int slices, long u_pair_stride, double p, double* slice_cost,
+                                        double* slice_theta, double* coef_s, double* coef_t, void* stream);
+
+/* Replaces: autograd through gather -> sort -> atan2 -> normalize -> matmul (:163-164, :270-279) on double tensors of
+ * two sizes: shw_ssw_backward_points_f64 with n != m allowed -- coef_s (pairs*slices*n), coef_t (pairs*slices*m),
+ * grad_xs (pairs, n, 3), grad_xt (pairs, m, 3); pair_w / total_w / scale as there; fixed-order sums. */
+SHW_API int shw_ssw_backward_points_general_f64(const double* xs, const double* xt, const double* dirs,
+                                                const double* coef_s, const double* coef_t, int pairs, int n, int m,
+                                                int slices, long u_pair_stride, double scale, const double* pair_w,
+                                                const double* total_w, double* grad_xs, double* grad_xt, void* stream);
+
+/* Replaces: binary_search_circle (:117-207) and emd1D_circle (:210-247) on double rows of circle coordinates with
+ * weights and / or n != m; `method` as in shw_circle_ot, weights as in shw_ssw_forward_general_f64 (per row).
+ *   u (rows, n), v (rows, m); cost (rows) out; aux (rows) out, may be NULL: the cut theta* or the median level;
+ *   grad_u (rows*n), grad_v (rows*m) out, both NULL for a value-only call. */
+SHW_API int shw_circle_ot_general_f64(const double* u, const double* v, const double* wu, const double* wv,
+                                      long wu_row_stride, long wv_row_stride, int rows, int n, int m, double p, int method,
+                                      double* cost, double* aux, double* grad_u, double* grad_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Euclidean sliced-Wasserstein (the notebooks' SWD baseline).

@@ -53,6 +53,19 @@ _SIGNATURES = {
                                           ctypes.c_void_p]),
     "shw_circle_ot_f64": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                          ctypes.c_int, _c_f32p, ctypes.c_void_p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    # general float64 path (csrc/shw_ssw_f64_general.hip): weighted and / or unequal-size clouds
+    "shw_max_points_f64_general": (ctypes.c_int, []),
+    "shw_ssw_forward_general_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long,
+                                                   ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_long, ctypes.c_double, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                   ctypes.c_void_p]),
+    "shw_ssw_backward_points_general_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int,
+                                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                                           ctypes.c_double, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                           ctypes.c_void_p]),
+    "shw_circle_ot_general_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                                 _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                        ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,

@@ -5,6 +5,8 @@
 // the float32 units -- sliced_cost (max_spherical_sliced_w.py:251-286, _fast.py:258-295), binary_search_circle
 // (:117-207), emd1D_circle (:210-247) -- when the caller's tensors are double (`dtype = u_values.dtype`, :153-160).
 //
+// Weighted and unequal-size double clouds are shw_ssw_f64_general.hip; the device helpers both units use (reductions,
+// |d|^p, circle coordinate, searches, the project-and-sort stage of one cloud) are f64_common.hpp.
 // This unit shares no kernel with the float32 path: those are tuned to the 32-bit word (registers per key, packed
 // (key, index) items, the degree-15 arctangent) and stay as they are.  Here ONE WORKGROUP owns one (pair, slice):
 //   1. projection (a, b) = U^T x as an FMA chain from +0 and coord = (atan2(-b, -a) + pi) / (2 pi) with the device
@@ -30,13 +32,12 @@
 
 #include "../../include/shw.h"
 #include "dispatch.hpp"      // host launch helpers only: no device code is shared with the float32 units
+#include "f64_common.hpp"    // reductions, |d|^p, circle coordinate, searches, the project-and-sort stage
 
 namespace shw {
 namespace f64 {
 
 constexpr int kItems = 4;            // sorted positions per thread and cloud: the workgroup has max(64, P / 4) threads
-constexpr int kMaxWaves = 16;
-constexpr unsigned kBinLimit = 24;   // more atoms than this in one bin: the cloud is sorted by the network
 constexpr int kFixedLds = 6 * kMaxWaves * 8 + (kMaxWaves + 2) * 4;   // reduction scratch, scan totals, flags
 
 struct Args {
@@ -54,51 +55,6 @@ struct Args {
   int p_int;                         // p as a small integer (1..8), else 0
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) v += __shfl_xor(v, s, 64);   // butterfly: the same bits in every lane
-  return v;
-}
-
-// Sum of three per-thread values over the workgroup, the same bits in every thread.  `red` holds two sets of
-// 3 x kMaxWaves partials used in turn, so one barrier per call is enough: a thread can only be one call ahead of
-// the slowest reader.
-__device__ __forceinline__ void block_sum3(double& a, double& b, double& c, double* red, int& turn, int nwaves) {
-  a = wave_sum_d(a); b = wave_sum_d(b); c = wave_sum_d(c);
-  double* r = red + turn * 3 * kMaxWaves;
-  turn ^= 1;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { r[wave] = a; r[kMaxWaves + wave] = b; r[2 * kMaxWaves + wave] = c; }
-  __syncthreads();
-  a = r[0]; b = r[kMaxWaves]; c = r[2 * kMaxWaves];
-  for (int w = 1; w < nwaves; ++w) { a += r[w]; b += r[kMaxWaves + w]; c += r[2 * kMaxWaves + w]; }
-}
-
-__device__ __forceinline__ double pow_abs(double d, double p, int p_int) {
-  const double a = fabs(d);
-  if (p_int == 2) return d * d;
-  if (p_int > 0) {
-    double r = a;
-    for (int i = 1; i < p_int; ++i) r *= a;
-    return r;
-  }
-  return pow(a, p);
-}
-
-// d/dD |D|^p (0 at D = 0, as the float32 kernels)
-__device__ __forceinline__ double dpow_abs(double d, double p, int p_int) {
-  const double a = fabs(d);
-  if (!(a > 0.0)) return 0.0;
-  double r;
-  if (p_int > 0) {
-    r = 1.0;
-    for (int i = 1; i < p_int; ++i) r *= a;
-  } else {
-    r = pow(a, p - 1.0);
-  }
-  return copysign(p * r, d);
-}
-
 // v_ext(q) = v[q mod n] + floor(q / n) for q in [-2n, 3n)
 __device__ __forceinline__ double target_ext(const double* sv, int q, int n, int* at = nullptr) {
   double turn = 0.0;
@@ -108,52 +64,6 @@ __device__ __forceinline__ double target_ext(const double* sv, int q, int n, int
   if (q >= n) { q -= n; turn += 1.0; }
   if (at) *at = q;
   return sv[q] + turn;
-}
-
-__device__ __forceinline__ double circle_coord(double a, double b) {
-  const double kPi = 3.141592653589793, kTwoPi = 6.283185307179586;
-  return (atan2(-b, -a) + kPi) / kTwoPi;
-}
-
-// number of keys < val (STRICT) or <= val among the first n of the ascending array
-template <bool STRICT>
-__device__ __forceinline__ int count_below(const double* buf, int n, double val) {
-  int lo = 0, hi = n;                  // answer in [lo, hi]
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    const double probe = buf[mid];
-    const bool go = STRICT ? (probe < val) : (probe <= val);
-    if (go) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// Bin of a coordinate among P equal bins of [0, 1] (P a power of two: the scaling is exact, the map monotone); anything
-// outside, which only rows of coordinates from a caller can hold, goes to the first or last bin.
-__device__ __forceinline__ int bin_of(double c, int P) {
-  const int bin = (int)(c * (double)P);
-  return max(0, min(P - 1, bin));
-}
-
-// Bitonic network over (coordinate, index) in LDS, all T threads; ends with a barrier.
-__device__ __forceinline__ void bitonic_sort(double* key, uint16_t* idx, int P, int t, int T) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int c = t; c < (P >> 1); c += T) {
-        const int i = ((c & ~(j - 1)) << 1) | (c & (j - 1));
-        const int h = i | j;
-        const double ka = key[i], kb = key[h];
-        const uint16_t ia = idx[i], ib = idx[h];
-        const bool gt = (ka > kb) || (ka == kb && ia > ib);
-        const bool up = (i & k) == 0;
-        if (gt == up) {
-          key[i] = kb; key[h] = ka;
-          idx[i] = ib; idx[h] = ia;
-        }
-      }
-      __syncthreads();
-    }
-  }
 }
 
 // LEVEL_MEDIAN false: min_k c(k) (any p >= 1).  true: the p = 1 level-median formula.
@@ -187,95 +97,9 @@ __global__ __launch_bounds__(1024) void ssw_f64_kernel(Args A) {
   double acc_u = 0.0, acc_v = 0.0, unused = 0.0;
   for (int which = 0; which < 2; ++which) {
     const double* X = (which ? A.xt : A.xs) + (long)b * n * A.pstride;
-    double* dst = which ? sv : su;
-    uint16_t* dsti = which ? pv : pu;
-    for (int bin = t; bin < P; bin += T) hist[bin] = 0;
-    __syncthreads();
-    double acc = 0.0;
-    for (int e = t; e < n; e += T) {
-      double c;
-      if (A.dirs) {
-        const double px = X[3 * e], py = X[3 * e + 1], pz = X[3 * e + 2];
-        const double a = fma(pz, U[4], fma(py, U[2], fma(px, U[0], 0.0)));
-        const double bb = fma(pz, U[5], fma(py, U[3], fma(px, U[1], 0.0)));
-        c = circle_coord(a, bb);
-      } else {
-        c = X[e] + 0.0;                                   // -0 -> +0
-      }
-      acc += c;
-      tmp[e] = c;
-      atomicAdd(&hist[bin_of(c, P)], 1u);
-    }
+    const double acc = project_and_sort(X, n, P, U, A.dirs != nullptr, which ? sv : su, which ? pv : pu, tmp, hist, wsum,
+                                        flags + which, t, T);
     if (which) acc_v = acc; else acc_u = acc;
-    __syncthreads();
-    // exclusive scan of the bin counts: thread t owns bins [t per, (t + 1) per)
-    {
-      const int per = (P + T - 1) / T, first = t * per;
-      unsigned local = 0;
-      for (int j = 0; j < per; ++j) {
-        const unsigned c = (first + j < P) ? hist[first + j] : 0u;
-        local += c;
-        if (c > kBinLimit) flags[which] = 1;              // a crowded bin: this cloud takes the network instead
-      }
-      unsigned incl = local;
-#pragma unroll
-      for (int sft = 1; sft < 64; sft <<= 1) {
-        const unsigned up = __shfl_up(incl, sft, 64);
-        if ((t & 63) >= sft) incl += up;
-      }
-      if ((t & 63) == 63) wsum[t >> 6] = incl;
-      __syncthreads();
-      unsigned run = incl - local;
-      for (int w = 0; w < (t >> 6); ++w) run += wsum[w];
-      for (int j = 0; j < per; ++j) {
-        if (first + j < P) {
-          const unsigned c = hist[first + j];
-          hist[first + j] = run;
-          run += c;
-        }
-      }
-    }
-    __syncthreads();
-    const bool network = flags[which] != 0;               // the same in every thread
-    if (!network) {
-      // scatter to the bins (the order inside a bin is whatever the counters gave), pads behind
-      for (int e = t; e < P; e += T) {
-        if (e < n) {
-          const double c = tmp[e];
-          const unsigned pos = atomicAdd(&hist[bin_of(c, P)], 1u);
-          dst[pos] = c;
-          dsti[pos] = (uint16_t)e;
-        } else {
-          dst[e] = __builtin_inf();
-          dsti[e] = (uint16_t)e;
-        }
-      }
-      __syncthreads();
-      // every bin into the total order (coordinate, index) by insertion: hist[bin] now is the bin's end
-      for (int bin = t; bin < P; bin += T) {
-        const int start = bin ? (int)hist[bin - 1] : 0, end = (int)hist[bin];
-        for (int i = start + 1; i < end; ++i) {
-          const double k = dst[i];
-          const uint16_t ki = dsti[i];
-          int j = i - 1;
-          while (j >= start && (dst[j] > k || (dst[j] == k && dsti[j] > ki))) {
-            dst[j + 1] = dst[j];
-            dsti[j + 1] = dsti[j];
-            --j;
-          }
-          dst[j + 1] = k;
-          dsti[j + 1] = ki;
-        }
-      }
-    } else {
-      for (int e = t; e < P; e += T) {
-        dst[e] = (e < n) ? tmp[e] : __builtin_inf();
-        dsti[e] = (uint16_t)e;
-      }
-      __syncthreads();
-      bitonic_sort(dst, dsti, P, t, T);
-    }
-    __syncthreads();
   }
 
   double* cs = A.coef_s ? A.coef_s + s * n : nullptr;
@@ -555,12 +379,6 @@ __global__ __launch_bounds__(256) void stiefel_frames_f64_kernel(const double* _
   U[0] = 1.0 - tau1; U[1] = q2x;
   U[2] = -tau1 * v1; U[3] = q2y;
   U[4] = -tau1 * v2; U[5] = q2z;
-}
-
-static int small_integer_power(double p) {
-  for (int k = 1; k <= 8; ++k)
-    if (p == (double)k) return k;
-  return 0;
 }
 
 // problems = pairs * slices workgroups; level_median selects the p = 1 formula

@@ -15,6 +15,11 @@ float64 for equal cloud sizes with uniform weights (any p >= 1, loss and gradien
 kernels of csrc/shw_ssw_f64.hip, up to `max_points_f64()` points per cloud).  Clouds and directions share one dtype.
 float64 is OPT-IN: until `enable_float64()` is called (or the process starts with SHW_FLOAT64=1) double tensors raise
 TypeError as they always did, so that a caller who passes double by accident is told instead of paying ~9x.
+Weighted and unequal-size double clouds are a SECOND opt-in on top of it, `enable_float64_general()` (or
+SHW_FLOAT64_GENERAL=1): kernels of csrc/shw_ssw_f64_general.hip, up to `max_points_f64_general()` points per cloud, the
+exact minimum over the cut for p != 1 and the level-median formula for p == 1.  While it is off such calls raise the
+ValueError they always raised, so that a loader that drops one point does not silently move a caller from the
+equal-size kernel to a much slower one.  Weights have the clouds' dtype and are not differentiable.
 """
 from __future__ import annotations
 
@@ -29,6 +34,7 @@ from . import _lib
 
 _FLOATS = (torch.float32, torch.float64)
 _float64_on = os.environ.get("SHW_FLOAT64", "0") == "1"
+_float64_general_on = os.environ.get("SHW_FLOAT64_GENERAL", "0") == "1"
 
 
 def enable_float64(on=True) -> bool:
@@ -42,6 +48,19 @@ def enable_float64(on=True) -> bool:
 
 def float64_enabled() -> bool:
     return _float64_on
+
+
+def enable_float64_general(on=True) -> bool:
+    """Accept float64 clouds of unequal sizes and / or with weights (the general circular-OT kernels in double; see the
+    module docstring).  Only effective together with `enable_float64()`.  Off by default: such calls then raise the
+    ValueError they raised before these kernels existed.  Process-wide; returns the previous setting."""
+    global _float64_general_on
+    previous, _float64_general_on = _float64_general_on, bool(on)
+    return previous
+
+
+def float64_general_enabled() -> bool:
+    return _float64_general_on
 
 
 def _check_dtype(name, t):
@@ -58,14 +77,29 @@ def max_points_f64() -> int:
     return int(_lib.load().shw_max_points_f64())
 
 
+def max_points_f64_general() -> int:
+    """Largest point count per cloud of the general float64 path (`shw_max_points_f64_general`)."""
+    return int(_lib.load().shw_max_points_f64_general())
+
+
 def _check_f64_shape(n, m, weighted):
-    """The float64 kernels cover the reference's own call shape only; everything else says so instead of failing in HIP."""
+    """Which float64 kernels serve the shape -- True: the general ones (weights and / or n != m, their own opt-in).
+    Everything they do not cover says so instead of failing in HIP."""
     if weighted or n != m:
-        raise ValueError("float64 input is supported for equal cloud sizes with uniform weights only (got "
-                         f"n = {n}, m = {m}{', weights' if weighted else ''}); weighted and unequal-size clouds are float32")
+        if not _float64_general_on:
+            raise ValueError("float64 input is supported for equal cloud sizes with uniform weights only (got "
+                             f"n = {n}, m = {m}{', weights' if weighted else ''}); weighted and unequal-size clouds are "
+                             "float32 unless the general float64 kernels are switched on: call enable_float64_general() "
+                             "(or set SHW_FLOAT64_GENERAL=1)")
+        limit = max_points_f64_general()
+        if n > limit or m > limit:
+            raise ValueError(f"float64 input with weights or unequal cloud sizes is supported up to {limit} points per "
+                             f"cloud, got n = {n}, m = {m}")
+        return True
     limit = max_points_f64()
     if n > limit:
         raise ValueError(f"float64 input is supported up to {limit} points per cloud, got {n}")
+    return False
 
 
 def _stream_ptr(device) -> int:
@@ -136,19 +170,22 @@ class SSWWorkspace:
     MAX_IDLE_BYTES = 4 << 30
 
     def __init__(self, key):
-        dev, _stream, B, n, m, L, dtype, with_coef = key
+        dev, _stream, B, n, m, L, dtype, general64, with_coef = key
         self.key = key
         self.pooled = True
         word = 4 if dtype == torch.float32 else 8
         self.slice_cost = torch.empty(B * L, dtype=dtype, device=dev)
         self.slice_aux = torch.empty(B * L, dtype=torch.int32, device=dev)     # shift k* / median level / cut bits
+        # general float64 path: the cut theta* / median level is a double, which the int32 words above cannot hold
+        self.slice_cut = torch.empty(B * L, dtype=dtype, device=dev) if (dtype == torch.float64 and general64) else None
         self.coef_s = torch.empty(B * L * n, dtype=dtype, device=dev) if with_coef else None
         self.coef_t = torch.empty(B * L * m, dtype=dtype, device=dev) if with_coef else None
-        self.nbytes = (word + 4) * B * L + (word * B * L * (n + m) if with_coef else 0)
+        self.nbytes = ((word + 4) * B * L + (word * B * L * (n + m) if with_coef else 0)
+                       + (8 * B * L if self.slice_cut is not None else 0))
 
     @classmethod
-    def lease(cls, dev, B, n, m, L, with_coef, dtype=torch.float32):
-        key = (torch.device(dev), _stream_ptr(dev), B, n, m, L, dtype, bool(with_coef))
+    def lease(cls, dev, B, n, m, L, with_coef, dtype=torch.float32, general64=False):
+        key = (torch.device(dev), _stream_ptr(dev), B, n, m, L, dtype, bool(general64), bool(with_coef))
         if torch.cuda.is_current_stream_capturing():
             ws = cls(key)
             ws.pooled = False
@@ -223,26 +260,35 @@ class _PairLosses(torch.autograd.Function):
         stride = 0 if shared_dirs else L * 6
         dtype = Xs.dtype
         f64 = dtype == torch.float64
-        ws = SSWWorkspace.lease(dev, B, n, m, L, need_grad, dtype)
+        weighted = wu is not None or wv is not None
+        general64 = f64 and (weighted or n != m)                # switched on and within the limit: checked by the caller
+        ws = SSWWorkspace.lease(dev, B, n, m, L, need_grad, dtype, general64)
         out = torch.empty(B + 2, dtype=dtype, device=dev)                # [pair_loss (B) | total (2)]
         stream = _stream_ptr(dev)
-        weighted = wu is not None or wv is not None
-        general = weighted or (float(p) != 1.0 and n != m)      # p == 1 with uniform weights: level-median kernel
+        general = general64 or weighted or (float(p) != 1.0 and n != m)   # p == 1 with uniform weights: level-median kernel
         cs = ws.coef_s.data_ptr() if need_grad else None
         ct = ws.coef_t.data_ptr() if need_grad else None
+
+        def wargs(w, cnt):
+            if w is None:
+                return None, 0
+            return w.data_ptr(), (0 if w.dim() == 1 else cnt)
         with torch.cuda.device(dev):
-            if f64:
+            if general64:
+                # n != m and / or weights in double: the exact minimum over the cut, or the level median at p == 1
+                wu_p, wu_s = wargs(wu, n)
+                wv_p, wv_s = wargs(wv, m)
+                _lib.check(lib.shw_ssw_forward_general_f64(
+                    Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), wu_p, wv_p, wu_s, wv_s, B, n, m, L, stride,
+                    float(p), ws.slice_cost.data_ptr(), ws.slice_cut.data_ptr(), cs, ct, stream),
+                    "shw_ssw_forward_general_f64")
+            elif f64:
                 # equal sizes, uniform weights (checked by the caller): one entry for loss and training form
                 _lib.check(lib.shw_ssw_forward_f64(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), B, n, m, L,
                                                    stride, float(p), ws.slice_cost.data_ptr(),
                                                    ws.slice_aux.data_ptr(), cs, ct, stream), "shw_ssw_forward_f64")
             elif general:
                 # n != m and / or weights: the reference's bisection over the cut, followed step for step
-
-                def wargs(w, cnt):
-                    if w is None:
-                        return None, 0
-                    return w.data_ptr(), (0 if w.dim() == 1 else cnt)
                 wu_p, wu_s = wargs(wu, n)
                 wv_p, wv_s = wargs(wv, m)
                 _lib.check(lib.shw_ssw_forward_general(
@@ -301,21 +347,25 @@ class _PairLosses(torch.autograd.Function):
                 gp = gp.clone() if gp is not None else torch.zeros(B, dtype=dtype, device=dev)
                 gp[0] += g_first.to(dtype)
         gt = g_total.to(dtype).contiguous() if g_total is not None else None
-        entry = lib.shw_ssw_backward_points if dtype == torch.float32 else lib.shw_ssw_backward_points_f64
+        name = ("shw_ssw_backward_points" if dtype == torch.float32 else
+                "shw_ssw_backward_points_general_f64" if ws.slice_cut is not None else "shw_ssw_backward_points_f64")
+        entry = getattr(lib, name)
         with torch.cuda.device(dev):
             _lib.check(entry(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
                              ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
                              1.0 / L, gp.data_ptr() if gp is not None else None,
                              gt.data_ptr() if gt is not None else None, gxs.data_ptr(),
-                             gxt.data_ptr(), _stream_ptr(dev)),
-                       "shw_ssw_backward_points" if dtype == torch.float32 else "shw_ssw_backward_points_f64")
+                             gxt.data_ptr(), _stream_ptr(dev)), name)
         return gxs, gxt, None, None, None, None, None, None, None
 
 
-def _check_weights(name, w, count, B, dev):
+def _check_weights(name, w, count, B, dev, dtype=torch.float32):
     if w is None:
         return None
-    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32:
+    if dtype == torch.float64:
+        if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float64:
+            raise TypeError(f"{name} must be a float64 device tensor, the dtype of the clouds")
+    elif not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32:
         raise TypeError(f"{name} must be a float32 device tensor")
     if tuple(w.shape) not in ((count,), (B, count)):
         raise ValueError(f"{name} must have shape ({count},) or ({B}, {count}), got {tuple(w.shape)}")
@@ -330,7 +380,8 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     [optionally also the (B,L) per-slice costs and optimal shifts; or, with return_total, the shape-[1] sum over
     pairs that the reduction kernel produces in the same launch (the batched reference value, _fast.py:291-293)].
     Scratch (per-slice arrays, gradient coefficients) lives in a pooled SSWWorkspace; results are fresh tensors.
-    Losses, per-slice costs and gradients have the input's dtype; float64 needs n == m and no weights."""
+    Losses, per-slice costs and gradients have the input's dtype; float64 with n != m or weights needs
+    `enable_float64_general()` and, like the float32 general path, returns a zero shift tensor with the slices."""
     _check_cloud("Xs", Xs)
     _check_cloud("Xt", Xt)
     _check_cloud_dirs(Us)
@@ -347,8 +398,8 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
         raise ValueError("need at least one slice and one point per cloud")
     if Xs.dtype == torch.float64:
         _check_f64_shape(Xs.shape[1], Xt.shape[1], u_weights is not None or v_weights is not None)
-    wu = _check_weights("u_weights", u_weights, Xs.shape[1], Xs.shape[0], Xs.device)
-    wv = _check_weights("v_weights", v_weights, Xt.shape[1], Xs.shape[0], Xs.device)
+    wu = _check_weights("u_weights", u_weights, Xs.shape[1], Xs.shape[0], Xs.device, Xs.dtype)
+    wv = _check_weights("v_weights", v_weights, Xt.shape[1], Xs.shape[0], Xs.device, Xs.dtype)
     # evaluation under torch.no_grad() on inputs that still carry requires_grad must not run the
     # training kernel / allocate the coefficient scratch
     need_grad = torch.is_grad_enabled() and (Xs.requires_grad or Xt.requires_grad)
@@ -415,7 +466,23 @@ class _CircleOT(torch.autograd.Function):
         cost = torch.empty(rows, dtype=u.dtype, device=dev)
         gu = torch.empty(rows, n, dtype=u.dtype, device=dev) if need_grad else None
         gv = torch.empty(rows, m, dtype=u.dtype, device=dev) if need_grad else None
-        if u.dtype == torch.float64:                # equal sizes, no weights (checked by the caller)
+        def wargs(w, cnt):
+            if w is None:
+                return None, 0
+            return w.data_ptr(), (0 if w.dim() == 1 else cnt)
+        wu_p, wu_s = wargs(wu, n)
+        wv_p, wv_s = wargs(wv, m)
+        if u.dtype == torch.float64 and (n != m or wu is not None or wv is not None):
+            # switched on and within the limit (checked by the caller)
+            with torch.cuda.device(dev):
+                _lib.check(lib.shw_circle_ot_general_f64(
+                    uc.data_ptr(), vc.data_ptr(), wu_p, wv_p, wu_s, wv_s, rows, n, m, float(p), int(method),
+                    cost.data_ptr(), None, gu.data_ptr() if need_grad else None, gv.data_ptr() if need_grad else None,
+                    _stream_ptr(dev)), "shw_circle_ot_general_f64")
+            if need_grad:
+                ctx.save_for_backward(gu, gv)
+            return cost
+        if u.dtype == torch.float64:                # equal sizes, no weights
             with torch.cuda.device(dev):
                 _lib.check(lib.shw_circle_ot_f64(uc.data_ptr(), vc.data_ptr(), rows, n, m, float(p), int(method),
                                                  cost.data_ptr(), None, gu.data_ptr() if need_grad else None,
@@ -424,13 +491,6 @@ class _CircleOT(torch.autograd.Function):
             if need_grad:
                 ctx.save_for_backward(gu, gv)
             return cost
-
-        def wargs(w, cnt):
-            if w is None:
-                return None, 0
-            return w.data_ptr(), (0 if w.dim() == 1 else cnt)
-        wu_p, wu_s = wargs(wu, n)
-        wv_p, wv_s = wargs(wv, m)
         with torch.cuda.device(dev):
             _lib.check(lib.shw_circle_ot(uc.data_ptr(), vc.data_ptr(), wu_p, wv_p, wu_s, wv_s, rows, n, m, float(p),
                                          int(method), cost.data_ptr(), None, gu.data_ptr() if need_grad else None,
@@ -467,8 +527,8 @@ def _circle_ot(u_values, v_values, u_weights, v_weights, p, method):
         if u.shape[1] < 1 or v.shape[1] < 1:
             raise ValueError("need at least one coordinate per row")
         _check_f64_shape(u.shape[1], v.shape[1], u_weights is not None or v_weights is not None)
-    wu = _check_weights("u_weights", u_weights, u.shape[1], u.shape[0], u.device)
-    wv = _check_weights("v_weights", v_weights, v.shape[1], u.shape[0], u.device)
+    wu = _check_weights("u_weights", u_weights, u.shape[1], u.shape[0], u.device, u.dtype)
+    wv = _check_weights("v_weights", v_weights, v.shape[1], u.shape[0], u.device, u.dtype)
     need_grad = torch.is_grad_enabled() and (u.requires_grad or v.requires_grad)
     return _CircleOT.apply(u, v, float(p), wu, wv, need_grad, method)
 
@@ -478,13 +538,16 @@ def binary_search_circle(u_values, v_values, u_weights=None, v_weights=None, p=1
     coordinates in [0, 1], (rows, n) and (rows, m) -> (rows,), by the bisection over the cut for EVERY p >= 1.  p = 1 is
     the reference's default and ends in `Cost`'s p == 1 branch (:107-108): the true circular W_1, up to 2.5 % away from
     what `emd1D_circle` returns (that formula leaves out the wrap segment; `sliced_cost` sends p == 1 there, :281-284).
-    Differentiable w.r.t. the coordinates (the cut is detached as at :207)."""
+    Differentiable w.r.t. the coordinates (the cut is detached as at :207).  Double rows with weights or n != m need
+    `enable_float64_general()` and return the exact minimum over the cut, which the reference's stopping rule ends up to
+    1.6e-11 above (fixture G14)."""
     return _circle_ot(u_values, v_values, u_weights, v_weights, p, _lib.CIRCLE_BISECTION)
 
 
 def emd1D_circle(u_values, v_values, u_weights=None, v_weights=None, p=1):
     """Reference `emd1D_circle` (:210-247): the level-median formula for p = 1, quirk included.
-    The reference function has no branch for p != 1 (it falls off its end and returns None); that is an error here."""
+    The reference function has no branch for p != 1 (it falls off its end and returns None); that is an error here.
+    Double rows with weights or n != m need `enable_float64_general()`."""
     if float(p) != 1.0:
         raise ValueError("emd1D_circle is the p = 1 level-median formula (the reference returns None for p != 1); "
                          "use binary_search_circle for p != 1")
