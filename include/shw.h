@@ -248,6 +248,59 @@ SHW_API int shw_circle_ot_general_f64(const double* u, const double* v, const do
                                       double* cost, double* aux, double* grad_u, double* grad_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spherical sliced-Wasserstein on S^(dim-1): points of dimension 2 <= dim <= 64, fp32 (additive to ABI 3).
+ * The reference reads the point dimension from its input (`d = Xs.shape[1]`, max_spherical_sliced_w.py:304; frames
+ * (L, d, 2), :307-308); only the projection (:270-271) and its backward depend on it.  These entries (kernels of
+ * csrc/shw_ssw_dim.hip) write the circle coordinates of both clouds to a workspace, run shw_circle_ot on them -- every
+ * size class, every p >= 1, n != m and weights -- and turn its gradient rows into point gradients:
+ *   clouds (pairs, points, dim); dirs (slices, dim, 2) shared (u_pair_stride = 0) or (pairs, slices, dim, 2)
+ *   (u_pair_stride >= slices*dim*2 floats).
+ * Limits: those of shw_circle_ot (8192 points per cloud; 4096 with weights, or with n != m at p != 1).  dim outside
+ * 2..64 or a size outside the limits returns 1 without touching the device.  dim = 3 is accepted and gives the
+ * coordinates of the R^3 kernels bit for bit (the same sum fma(x_d, U[d][k], acc), d ascending from +0).
+ */
+
+/* Largest point dimension of the entries of this section (64). */
+SHW_API int shw_max_point_dim(void);
+
+/* Replaces: `U, _ = torch.linalg.qr(Z)` (:308) for Z (count, dim, 2), as shw_stiefel_frames: two Householder steps with
+ * LAPACK's sign convention, one thread per matrix.  z (count, dim, 2) in, u (count, dim, 2) out. */
+SHW_API int shw_stiefel_frames_dim(const float* z, long count, int dim, float* u, void* stream);
+
+/* Replaces: projection, normalise and circle coordinate (:270-279) of ONE cloud.
+ *   x (pairs, n, dim); coords (pairs*slices*n) out: coords[(b*slices + l)*n + i] in [0, 1], the coordinate of point i
+ *   of pair b on the great circle of frame l.  An all-zero point gets coordinate 0. */
+SHW_API int shw_ssw_coords_dim(const float* x, const float* dirs, int pairs, int n, int dim, int slices,
+                               long u_pair_stride, float* coords, void* stream);
+
+/* Bytes of the workspace of shw_ssw_forward_dim: the two coordinate arrays, 4 * pairs * slices * (n + m). */
+SHW_API size_t shw_ssw_dim_workspace_bytes(int pairs, int n, int m, int slices);
+
+/* Replaces: sliced_cost (:251-286, _fast.py:258-295) up to, not including, the mean over slices, for any dim:
+ * shw_ssw_coords_dim on both clouds, then shw_circle_ot with SHW_CIRCLE_AS_SLICED on the pairs*slices rows.
+ *   wu (n) or (pairs, n), wv (m) or (pairs, m): weights as in shw_ssw_forward_general, NULL = uniform;
+ *   w*_pair_stride = 0 for a row shared by all pairs (one circle-level launch), else the floats between consecutive
+ *   pairs' rows (one circle-level launch per pair);
+ *   workspace : shw_ssw_dim_workspace_bytes(pairs, n, m, slices) bytes; holds the coordinates after the call;
+ *   slice_cost (pairs*slices) out; slice_aux (pairs*slices) out, may be NULL: `aux` of shw_circle_ot (int32 shift or
+ *   median level, or the fp32 cut);
+ *   coef_s (pairs*slices*n), coef_t (pairs*slices*m) out, both NULL for a loss-only call: d cost(b,l) / d coord in
+ *   ORIGINAL point order, the input of shw_ssw_backward_points_dim. */
+SHW_API int shw_ssw_forward_dim(const float* xs, const float* xt, const float* dirs, const float* wu, const float* wv,
+                                long wu_pair_stride, long wv_pair_stride, int pairs, int n, int m, int dim, int slices,
+                                long u_pair_stride, float p, void* workspace, float* slice_cost, float* slice_aux,
+                                float* coef_s, float* coef_t, void* stream);
+
+/* shw_ssw_backward_points for any dim (n != m allowed): grad_xs (pairs, n, dim), grad_xt (pairs, m, dim),
+ *   grad_x[b,i,:] = scale (pair_w[b] + total_w[0]) sum_l coef[b,l,i] (-b_ U_l[:,0] + a_ U_l[:,1]) / (2 pi (a_^2 + b_^2)),
+ *   (a_, b_) = U_l^T x[b,i] recomputed from the point, zero where a_^2 + b_^2 == 0; pair_w / total_w as there.
+ * One thread owns a gradient row and adds the slices in ascending order: bit-identical from run to run. */
+SHW_API int shw_ssw_backward_points_dim(const float* xs, const float* xt, const float* dirs, const float* coef_s,
+                                        const float* coef_t, int pairs, int n, int m, int dim, int slices,
+                                        long u_pair_stride, float scale, const float* pair_w, const float* total_w,
+                                        float* grad_xs, float* grad_xt, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Euclidean sliced-Wasserstein (the notebooks' SWD baseline).
  * Replaces: sliced_wasserstein_distance (Wasserstein_flow_problem/Flow_cube.ipynb:280-292): projection on unit
  * directions, per-slice sort of both projected sequences, sum of |sorted difference|^p.

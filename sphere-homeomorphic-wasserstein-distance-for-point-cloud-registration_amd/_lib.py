@@ -66,6 +66,20 @@ _SIGNATURES = {
     "shw_circle_ot_general_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                                  _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    # points of dimension 2..64 (csrc/shw_ssw_dim.hip): coordinates, circle-level solve, point gradients
+    "shw_max_point_dim": (ctypes.c_int, []),
+    "shw_stiefel_frames_dim": (ctypes.c_int, [_c_f32p, ctypes.c_long, ctypes.c_int, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_coords_dim": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_long, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_dim_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_ssw_forward_dim": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_long, ctypes.c_float, ctypes.c_void_p, _c_f32p, ctypes.c_void_p,
+                                           _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_backward_points_dim": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                                   ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                   ctypes.c_void_p]),
     "shw_esw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                        ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,

@@ -15,6 +15,9 @@ float64 for equal cloud sizes with uniform weights (any p >= 1, loss and gradien
 kernels of csrc/shw_ssw_f64.hip, up to `max_points_f64()` points per cloud).  Clouds and directions share one dtype.
 float64 is OPT-IN: until `enable_float64()` is called (or the process starts with SHW_FLOAT64=1) double tensors raise
 TypeError as they always did, so that a caller who passes double by accident is told instead of paying ~9x.
+Points of dimension d != 3 (clouds (B,n,d) on S^(d-1), frames (..., d, 2), 2 <= d <= 64 = `shw_max_point_dim()`) are float32: the
+kernels of csrc/shw_ssw_dim.hip write the circle coordinates, the circle-level solvers run on those rows, and a D-generic
+kernel turns their gradient rows into point gradients (`_PairLossesDim`).  d = 3 keeps its own kernels.
 Weighted and unequal-size double clouds are a SECOND opt-in on top of it, `enable_float64_general()` (or
 SHW_FLOAT64_GENERAL=1): kernels of csrc/shw_ssw_f64_general.hip, up to `max_points_f64_general()` points per cloud, the
 exact minimum over the cut for p != 1 and the level-median formula for p == 1.  While it is off such calls raise the
@@ -116,6 +119,26 @@ def _check_cloud(name, t):
         raise ValueError(f"{name} must have 3 coordinates per point, got shape {tuple(t.shape)}")
 
 
+def _check_point_dim(name, t, d):
+    """d != 3 on the spherical path: the D-generic kernels -- 2..shw_max_point_dim() coordinates, float32."""
+    most = int(_lib.load().shw_max_point_dim())
+    if not 2 <= d <= most:
+        raise ValueError(f"{name}: the point dimension must be in 2..{most}, got {d} (shape {tuple(t.shape)})")
+    if t.dtype == torch.float64:
+        raise ValueError(f"{name}: the D-generic path (point dimension {d} != 3) is float32; float64 input needs "
+                         "3 coordinates per point")
+
+
+def _check_sphere_cloud(name, t):
+    """A cloud of the spherical sliced-W functions: `_check_cloud` (R^3; also the check of Chamfer and Sinkhorn, whose
+    kernels know 3 coordinates only) or, for another last dimension, the D-generic path's range and dtype."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dim() >= 1 and t.shape[-1] != 3:
+        _check_point_dim(name, t, t.shape[-1])
+        _check_dtype(name, t)
+        return
+    _check_cloud(name, t)
+
+
 def draw_directions(num_projections, device, batch=None, d=3, dtype=None):
     """Uniform samples on the Stiefel manifold V_{d,2} from the GLOBAL torch generator, consumed exactly
     like the reference (randn of (L,d,2) resp. (B,L,d,2) on `device`, then reduced QR; :307-308,
@@ -127,14 +150,24 @@ def draw_directions(num_projections, device, batch=None, d=3, dtype=None):
 
 
 def stiefel_frames(Z):
-    """Reduced QR `U, _ = torch.linalg.qr(Z)` of (..., 3, 2) Gaussian matrices.  On the device this is the HIP
+    """Reduced QR `U, _ = torch.linalg.qr(Z)` of (..., d, 2) Gaussian matrices.  On the device this is the HIP
     kernel `shw_stiefel_frames` (LAPACK's Householder steps and sign convention, one thread per matrix):
     torch.linalg.qr itself takes ~0.94 s for the 32 768 frames of config 3 on MI355X, and differs from the CPU
     LAPACK result by up to 6e-6; the kernel takes microseconds and agrees with LAPACK to fp32 rounding.  CPU
     tensors (tests of the generator stream) go through torch.linalg.qr.  float64 input runs the double form of the
-    kernel (`shw_stiefel_frames_f64`) and agrees with LAPACK to double rounding."""
+    kernel (`shw_stiefel_frames_f64`) and agrees with LAPACK to double rounding.  d != 3 (2..64, float32) runs the
+    D-generic kernel `shw_stiefel_frames_dim`."""
     if not Z.is_cuda:
         return torch.linalg.qr(Z)[0]
+    if Z.dtype in _FLOATS and Z.dim() >= 2 and Z.shape[-1] == 2 and Z.shape[-2] != 3:
+        d = Z.shape[-2]
+        _check_point_dim("Z", Z, d)
+        Zc = Z.contiguous()
+        U = torch.empty_like(Zc)
+        with torch.cuda.device(Z.device):
+            _lib.check(_lib.load().shw_stiefel_frames_dim(Zc.data_ptr(), Zc.numel() // (2 * d), d, U.data_ptr(),
+                                                          _stream_ptr(Z.device)), "shw_stiefel_frames_dim")
+        return U
     if Z.dtype not in _FLOATS or tuple(Z.shape[-2:]) != (3, 2):
         raise TypeError("stiefel_frames expects float32 or float64 (..., 3, 2)")
     lib = _lib.load()
@@ -359,6 +392,83 @@ class _PairLosses(torch.autograd.Function):
         return gxs, gxt, None, None, None, None, None, None, None
 
 
+class _PairLossesDim(torch.autograd.Function):
+    """_PairLosses for points of any dimension 2..64 in float32: (B,n,d), (B,m,d), dirs (L,d,2) / (B,L,d,2) -> the same
+    five outputs.  The circle coordinates of both clouds are written out (4 B L (n + m) bytes from the caching allocator,
+    given back when forward returns), `shw_circle_ot` solves the B L rows, and backward runs the D-generic point-gradient
+    kernel on the coefficient rows kept in the leased workspace."""
+
+    @staticmethod
+    def forward(ctx, Xs, Xt, Us, p, shared_dirs, wu, wv, need_grad, want_slices):
+        lib = _lib.load()
+        B, n, d = Xs.shape
+        m = Xt.shape[1]
+        L = Us.shape[-3]
+        dev = Xs.device
+        Xs_c, Xt_c, Us_c = Xs.contiguous(), Xt.contiguous(), Us.contiguous()
+        stride = 0 if shared_dirs else L * d * 2
+        ws = SSWWorkspace.lease(dev, B, n, m, L, need_grad, torch.float32)
+        out = torch.empty(B + 2, dtype=torch.float32, device=dev)        # [pair_loss (B) | total (2)]
+        coords = torch.empty(B * L * (n + m), dtype=torch.float32, device=dev)
+        stream = _stream_ptr(dev)
+        general = wu is not None or wv is not None or (float(p) != 1.0 and n != m)
+
+        def wargs(w, cnt):
+            if w is None:
+                return None, 0
+            return w.data_ptr(), (0 if w.dim() == 1 else cnt)
+        wu_p, wu_s = wargs(wu, n)
+        wv_p, wv_s = wargs(wv, m)
+        with torch.cuda.device(dev):
+            _lib.check(lib.shw_ssw_forward_dim(
+                Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), wu_p, wv_p, wu_s, wv_s, B, n, m, d, L, stride,
+                float(p), coords.data_ptr(), ws.slice_cost.data_ptr(), ws.slice_aux.data_ptr(),
+                ws.coef_s.data_ptr() if need_grad else None, ws.coef_t.data_ptr() if need_grad else None, stream),
+                "shw_ssw_forward_dim")
+            _lib.check(lib.shw_ssw_reduce(ws.slice_cost.data_ptr(), B, L, 1.0 / L, out.data_ptr(),
+                                          out.data_ptr() + 4 * B, stream), "shw_ssw_reduce")
+        cost2d = shift2d = None
+        if want_slices:
+            cost2d = ws.slice_cost.view(B, L).clone()
+            shift2d = torch.zeros(B, L, dtype=torch.int32, device=dev) if general else ws.slice_aux.view(B, L).clone()
+            ctx.mark_non_differentiable(cost2d, shift2d)
+        if need_grad:
+            ctx.save_for_backward(Xs_c, Xt_c, Us_c)
+            ctx.lease = _Lease(ws)                  # the coefficients stay put until this node dies
+            ctx.dims = (B, n, m, d, L, stride)
+            ctx.set_materialize_grads(False)
+        else:
+            ws.release()
+        return out[:B], out[B:B + 1], cost2d, shift2d, out[0:1].view(())
+
+    @staticmethod
+    def backward(ctx, g_pair, g_total, _g_cost, _g_shift, g_first=None):
+        lib = _lib.load()
+        Xs_c, Xt_c, Us_c = ctx.saved_tensors
+        ws = ctx.lease.ws
+        B, n, m, d, L, stride = ctx.dims
+        dev = Xs_c.device
+        if g_pair is None and g_total is None and g_first is None:
+            return (None,) * 9
+        gxs = torch.empty_like(Xs_c)
+        gxt = torch.empty_like(Xt_c)
+        gp = g_pair.to(torch.float32).contiguous() if g_pair is not None else None
+        if g_first is not None:                     # gradient of the 0-dim first-pair output: belongs to row 0
+            if gp is None and B == 1:
+                gp = g_first.to(torch.float32).reshape(1)
+            else:
+                gp = gp.clone() if gp is not None else torch.zeros(B, dtype=torch.float32, device=dev)
+                gp[0] += g_first.to(torch.float32)
+        gt = g_total.to(torch.float32).contiguous() if g_total is not None else None
+        with torch.cuda.device(dev):
+            _lib.check(lib.shw_ssw_backward_points_dim(
+                Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, d,
+                L, stride, 1.0 / L, gp.data_ptr() if gp is not None else None,
+                gt.data_ptr() if gt is not None else None, gxs.data_ptr(), gxt.data_ptr(), _stream_ptr(dev)),
+                "shw_ssw_backward_points_dim")
+        return gxs, gxt, None, None, None, None, None, None, None
+
+
 def _check_weights(name, w, count, B, dev, dtype=torch.float32):
     if w is None:
         return None
@@ -375,23 +485,28 @@ def _check_weights(name, w, count, B, dev, dtype=torch.float32):
 def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weights=None, return_total=False,
                     return_first=False):
     """Core op: batched clouds (B,n,3), (B,m,3); directions (B,L,3,2) or shared (L,3,2); optional weights
-    (n,) / (B,n) and (m,) / (B,m).
+    (n,) / (B,n) and (m,) / (B,m).  Float32 clouds (B,n,d), (B,m,d) with directions (..., d, 2) of the same d in
+    2..64 take the D-generic path (`_PairLossesDim`), with the same outputs and options.
     Returns (B,) per-pair losses = mean over slices of W_p^p on the slice circle
     [optionally also the (B,L) per-slice costs and optimal shifts; or, with return_total, the shape-[1] sum over
     pairs that the reduction kernel produces in the same launch (the batched reference value, _fast.py:291-293)].
     Scratch (per-slice arrays, gradient coefficients) lives in a pooled SSWWorkspace; results are fresh tensors.
     Losses, per-slice costs and gradients have the input's dtype; float64 with n != m or weights needs
     `enable_float64_general()` and, like the float32 general path, returns a zero shift tensor with the slices."""
-    _check_cloud("Xs", Xs)
-    _check_cloud("Xt", Xt)
+    _check_sphere_cloud("Xs", Xs)
+    _check_sphere_cloud("Xt", Xt)
     _check_cloud_dirs(Us)
     if not (Xs.dtype == Xt.dtype == Us.dtype):
         raise TypeError(f"Xs, Xt and Us must share one dtype, got {Xs.dtype}, {Xt.dtype}, {Us.dtype}")
+    d = Xs.shape[-1]
+    if Xt.shape[-1] != d or Us.shape[-2] != d:
+        raise ValueError(f"point dimension mismatch: Xs has {d} coordinates per point, Xt {Xt.shape[-1]} and the frames "
+                         f"Us {Us.shape[-2]} (clouds (B,n,d), (B,m,d) and frames (L,d,2) or (B,L,d,2) share one d)")
     if Xs.dim() != 3 or Xt.dim() != 3 or Xs.shape[0] != Xt.shape[0]:
-        raise ValueError("Xs and Xt must be (B,n,3) and (B,m,3) with the same B")
+        raise ValueError(f"Xs and Xt must be (B,n,{d}) and (B,m,{d}) with the same B")
     shared = Us.dim() == 3
     if not shared and Us.shape[0] != Xs.shape[0]:
-        raise ValueError("per-pair directions must be (B,L,3,2)")
+        raise ValueError(f"per-pair directions must be (B,L,{d},2)")
     if not (float(p) >= 1.0):
         raise ValueError("p must be >= 1")
     if Us.shape[-3] < 1 or Xs.shape[1] < 1 or Xt.shape[1] < 1:
@@ -403,8 +518,9 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     # evaluation under torch.no_grad() on inputs that still carry requires_grad must not run the
     # training kernel / allocate the coefficient scratch
     need_grad = torch.is_grad_enabled() and (Xs.requires_grad or Xt.requires_grad)
-    pair, total, cost, shift, first = _PairLosses.apply(Xs, Xt, Us.detach(), float(p), shared, wu, wv, need_grad,
-                                                        bool(return_slices))
+    op = _PairLosses if d == 3 else _PairLossesDim
+    pair, total, cost, shift, first = op.apply(Xs, Xt, Us.detach(), float(p), shared, wu, wv, need_grad,
+                                               bool(return_slices))
     if return_first:                                # 0-dim loss of the first pair (the per-pair call shape)
         return first
     if return_total:
@@ -417,9 +533,43 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
 def _check_cloud_dirs(Us):
     if not isinstance(Us, torch.Tensor) or not Us.is_cuda:
         raise TypeError("Us must be a float32 or float64 device tensor")
+    if Us.dim() in (3, 4) and Us.shape[-1] == 2 and Us.shape[-2] != 3:
+        _check_point_dim("Us", Us, Us.shape[-2])
+        _check_dtype("Us", Us)
+        return
     _check_dtype("Us", Us)
     if Us.dim() not in (3, 4) or tuple(Us.shape[-2:]) != (3, 2):
         raise ValueError(f"Us must be (L,3,2) or (B,L,3,2), got {tuple(Us.shape)}")
+
+
+def circle_coordinates(X, Us):
+    """Circle coordinates of the reference's lines :270-279: X (B,n,d) and frames Us (L,d,2) shared or (B,L,d,2) ->
+    (B,L,n) numbers in [0, 1], `coords[b,l,i]` = (atan2(-b, -a) + pi) / (2 pi) with (a, b) = U_l^T x_i.  A cloud (n,d)
+    with frames (L,d,2) gives (L,n).  Float32, 2 <= d <= 64 (d = 3 included: the same bits as the R^3 kernels compute
+    internally); not differentiable.  What `binary_search_circle` / `emd1D_circle` take as rows."""
+    _check_sphere_cloud("X", X)
+    _check_cloud_dirs(Us)
+    if X.dtype != torch.float32 or Us.dtype != torch.float32:
+        raise TypeError(f"circle_coordinates is float32, got {X.dtype} and {Us.dtype}")
+    single = X.dim() == 2
+    Xb = X.detach().unsqueeze(0) if single else X.detach()
+    d = Xb.shape[-1]
+    if Xb.dim() != 3 or Us.shape[-2] != d:
+        raise ValueError(f"point dimension mismatch or bad shape: X {tuple(X.shape)} must be (B,n,d) or (n,d) and Us "
+                         f"{tuple(Us.shape)} (L,d,2) or (B,L,d,2) with the same d")
+    B, n, _ = Xb.shape
+    shared = Us.dim() == 3
+    if not shared and Us.shape[0] != B:
+        raise ValueError(f"per-pair directions must be (B,L,{d},2)")
+    L = Us.shape[-3]
+    if n < 1 or L < 1:
+        raise ValueError("need at least one slice and one point")
+    Xc, Uc = Xb.contiguous(), Us.detach().contiguous()
+    out = torch.empty(B, L, n, dtype=torch.float32, device=X.device)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.load().shw_ssw_coords_dim(Xc.data_ptr(), Uc.data_ptr(), B, n, d, L, 0 if shared else L * d * 2,
+                                                  out.data_ptr(), _stream_ptr(X.device)), "shw_ssw_coords_dim")
+    return out[0] if single else out
 
 
 def sliced_cost(Xs, Xt, Us, p=2, u_weights=None, v_weights=None):
