@@ -167,8 +167,8 @@ __device__ __forceinline__ int binsort_scan(unsigned* cnt, int lane) {
 //   * NaN -> the low bits of a NaN: 0 for the canonical quiet NaN, always a multiple of 4 below 4 NB (full classes are
 //     powers of two), i.e. inside the counters (in bounds; NaN input has no defined order anyway);
 //   * the map does NOT saturate: 1.5 -> bin (NB - 1) / 2, -0.25 -> NB / 2, +inf -> 0.  Keys outside [0, 1] must not come
-//     here.  Projected coordinates never are: circle_coord (ssw_common.hpp) returns (ang + pi) (1 / 2 pi) with ang in
-//     [-fl(pi), fl(pi)], so the largest value is fl(2 fl(pi) fl(1 / 2 pi)) = 1.0 exactly and the smallest +0.  Pads (+inf)
+//     here.  Projected coordinates never are: circle_coord (ssw_common.hpp) returns P +- (r' - 1/8) with P one of 1/8, 3/8,
+//     5/8, 7/8 exactly and r' - 1/8 in [-1/8, +0], so the largest value is 1.0 exactly and the smallest +0.  Pads (+inf)
 //     do not exist in the full classes, the only ones that use this map.  Rows of caller-supplied coordinates
 //     (shw_circle_ot) are tested by binsort_keys_fit and take the network when a value is out of range (wave_sort_binned).
 template <int NB>

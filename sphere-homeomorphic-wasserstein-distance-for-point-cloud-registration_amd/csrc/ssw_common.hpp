@@ -84,14 +84,30 @@ __device__ __forceinline__ void load_frame(const float* dirs, long offset, float
 // circle coordinate of one projected point (reference :274-279):
 //     coord = (atan2(-b, -a) + pi) / (2 pi)
 // F.normalize (:274-275) is a positive rescale and cannot change the angle, so it is skipped.
-// atan2 is evaluated as atan(min/max) with a degree-15 odd minimax polynomial
-// (t + t^3 Q(t^2); with the 1.5-ulp quotient the total error is <= 1.9e-7 rad, rms 5.5e-8 rad, i.e.
-// <= 3e-8 in coordinate units = half an fp32 ulp of a coordinate in [0.5, 1)) and octant fix-ups that
-// follow the IEEE
-// signed-zero rules the reference relies on: a = b = +0 gives atan2(-0,-0) = -pi, i.e. coord 0.
-// Range: r ends in [0, fl(pi)], so ang lies in [-fl(pi), fl(pi)] and ang + fl(pi) in [+0, 2 fl(pi)] (exact); times
-// fl(1 / 2 pi) the largest value rounds to 1.0 exactly (2 fl(pi) fl(1 / 2 pi) = 1 - 1.3e-8, nearer to 1 than to the float
-// below it): every coordinate is in [0, 1], the domain of the bin map of bin_sort.hpp.
+// The coordinate is measured in turns from the start, with no angle in radians in between:
+//     coord = K + sigma r',     r' = atan(mn / mx) / (2 pi) in [0, 1/8],  mn = min(|a|, |b|),  mx = max(|a|, |b|)
+// r' = t q(t^2), t = mn / mx, q the degree-14 even polynomial whose coefficients are 1 / (2 pi) times those of the
+// degree-15 odd minimax arctangent (1, c3 .. c15), scaled in double and rounded once.  K and sigma depend only on
+// (A, B, S) = (sign bit of a, sign bit of b, |b| > |a|).  With alpha = 1 - 2 A, beta = 1 - 2 B, gamma = 1 - 2 S the three
+// reflections of atan2 (about the diagonal, about the y-axis, about the x-axis) compose to sigma = alpha beta gamma and
+//     (A, B, S)   000  001  010  011  100  101  110  111
+//     8 K           0    2    8    6    4    2    4    6        (coord = 0 + r', 1/4 - r', 1 - r', 3/4 + r', ...)
+// which is K = 1/2 - beta / 4 - alpha beta / 8 - alpha beta gamma / 8, hence
+//     coord = ((1/2 - beta / 4) - alpha beta / 8) + alpha beta gamma (r' - 1/8).
+// Every sign is one XOR of sign bits onto a constant or onto r' - 1/8 (full-rate bit operations: no compare, no select).
+// S is the sign bit of |a| - |b| (clear when they are equal: the diagonal belongs to the octant next to the x-axis).
+// Signed zeros follow the IEEE rules of atan2(-b, -a) that the reference relies on, through the sign BITS of a and b:
+// (+0, +0) -> +0, (-0, +-0) -> 1/2, (+0, -0) -> 1; points on the axes land on 0, 1/4, 1/2, 3/4, 1 exactly (r' = 0).
+// Error: the partial sums 1/2 - beta / 4 - alpha beta / 8 are multiples of 1/8 and exact; r' - 1/8 = fma(t, q, -1/8) lies
+// in [-1/8, 0] and rounds once, by at most 2^-28 (2^-29 once r' > 1/16), so what remains is the error of t and q (1.5-ulp
+// quotient, polynomial) and the rounding of the last add (<= 2^-25 in [1/2, 1)): <= 6e-8 in coordinate units against
+// float64 atan2, rms 1.5e-8, measured over 2.2e7 points by the numpy restatement in tests/test_circle_coord_cpu.py (on
+// the device, with its 1-ulp reciprocal: tests/test_circle_coord_gpu.py).
+// Range: q(1) sums to 0.12499998 <= 1/8 and t q is largest at t = 1 (the restatement checks the 2e5 floats below 1 too),
+// so r' - 1/8 is in [-1/8, +0] and never changes sign.  The exact partial sum is the octant's diagonal seam (1/8, 3/8,
+// 5/8 or 7/8), and sigma (r' - 1/8) leads from it towards the octant's axis, at most 1/8 away, and never to the
+// diagonal's other side: every coordinate is in [0, 1], the domain of the bin map of bin_sort.hpp, and the octants meet
+// in order at all eight seams.
 // Domain note: |a|,|b| below 1e-37 (denormal-scale projections) are treated as if max(|a|,|b|) were
 // 1e-37, i.e. the angle of such a vector is not resolved; exact zeros are handled exactly.
 __device__ __forceinline__ float circle_coord(float a, float b) {
@@ -99,19 +115,22 @@ __device__ __forceinline__ float circle_coord(float a, float b) {
   const float mx = fmaxf(fmaxf(ax, ay), 1e-37f), mn = fminf(ax, ay);
   const float t = mn * __builtin_amdgcn_rcpf(mx);  // v_rcp_f32 (1 ulp) * mn: t = mn/mx to 1.5 ulp
   const float s = t * t;
-  float q = -4.3554045260e-03f;
-  q = fmaf(q, s, 2.3040132597e-02f);
-  q = fmaf(q, s, -5.7773582637e-02f);
-  q = fmaf(q, s, 9.7942344844e-02f);
-  q = fmaf(q, s, -1.3976581395e-01f);
-  q = fmaf(q, s, 1.9962704182e-01f);
-  q = fmaf(q, s, -3.3331659436e-01f);
-  float r = fmaf(t * s, q, t);                     // atan(mn/mx) in [0, pi/4]
-  r = (ay > ax) ? 1.57079637050628662f - r : r;    // angle from the x-axis, [0, pi/2]
-  // x = -a is "negative" (incl. -0) exactly when the sign bit of a is clear
-  r = (__builtin_bit_cast(int, a) >= 0) ? 3.14159274101257324f - r : r;
-  const float ang = copysignf(r, -b);              // sign of y = -b (incl. signed zero)
-  return (ang + 3.14159274101257324f) * 0.159154936671257019f;
+  float q = -6.9318414899e-04f;
+  q = fmaf(q, s, 3.6669510882e-03f);
+  q = fmaf(q, s, -9.1949515045e-03f);
+  q = fmaf(q, s, 1.5588007867e-02f);
+  q = fmaf(q, s, -2.2244419903e-02f);
+  q = fmaf(q, s, 3.1771630049e-02f);
+  q = fmaf(q, s, -5.3048983216e-02f);
+  q = fmaf(q, s, 1.5915493667e-01f);
+  const float d = fmaf(t, q, -0.125f);             // r' - 1/8, r' = t q = atan(mn/mx) / (2 pi): one rounding, in [-1/8, +0]
+  const uint32_t sg = 0x80000000u;
+  const uint32_t ia = __builtin_bit_cast(uint32_t, a), ib = __builtin_bit_cast(uint32_t, b);
+  const uint32_t id = __builtin_bit_cast(uint32_t, ax - ay), x2 = ia ^ ib;
+  const float w1 = __builtin_bit_cast(float, 0xBE800000u ^ (ib & sg));                      // -beta / 4
+  const float w2 = __builtin_bit_cast(float, 0xBE000000u ^ (x2 & sg));                      // -alpha beta / 8
+  const float t3 = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, d) ^ ((x2 ^ id) & sg));   // alpha beta gamma d
+  return ((0.5f + w1) + w2) + t3;
 }
 
 // |d|^p.  PMODE 2: p == 2 (the reference's own call sites all use p = 2); PMODE 0: any p >= 1,
