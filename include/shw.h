@@ -344,6 +344,56 @@ SHW_API int shw_esw_backward_dirs_dim(const float* xs, const float* xt, const fl
                                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Generalised sliced-Wasserstein (csrc/shw_gsw.hip): the sort-and-difference of the notebooks' GSWD / max-GSWD /
+ * DSWD family (Wasserstein_flow_problem/Flow_cube.ipynb, the cell that starts with `def rand_projections`) for
+ * defining functions other than a dot product with a direction.  float32.
+ *
+ * Rows of keys the caller computed.  Replaces the sort / |difference|^p / sum lines of gsw_nn_1, gsw_nn_3,
+ * max_gsw_nn_1 and max_gsw_nn_3 (keys = the transposed output of the caller's network), and serves any other
+ * defining function evaluated in torch.
+ *   u, v (rows, n) contiguous; 1 <= n <= 4096; p >= 1; rows >= 0, any count.
+ *   row_sum (rows) out : sum_i |u_(i) - v_(i)|^p, u_(.) and v_(.) the rows sorted ascending.
+ *   coef_u / coef_v (rows, n) out, both NULL for a value-only call : d row_sum[r] / d u[r,i] and d row_sum[r] / d v[r,i]
+ *   in original element order (d|D|^p/dD of the sorted difference scattered through the sort's indices, negated for
+ *   v; 0 at a zero difference for p = 1, as the Euclidean entries).
+ * Returns hipErrorInvalidValue on a null pointer (other than both coefficient rows), one coefficient row without the
+ * other, n outside 1..4096, rows < 0 or p < 1. */
+SHW_API int shw_gsw_rows_forward(const float* u, const float* v, long rows, int n, float p, float* row_sum,
+                                 float* coef_u, float* coef_v, void* stream);
+
+/* Circular defining function g(x, theta) = || x - r theta ||_2, fused: keys, sorts and sums in one kernel, no
+ * (pairs, slices, n) key matrix in memory.  Replaces GSWD_circular, max_GSWD_circular and circular_function.
+ *   xs, xt (pairs, n, dim), 1 <= dim <= 64, 1 <= n <= 4096; thetas (slices, dim) shared (theta_pair_stride = 0) or
+ *   (pairs, slices, dim) (stride >= slices*dim); r any float; p >= 1; pairs * slices < 2^31.
+ *   The key of point i on slice l is sqrt(sum_d (x[i,d] - r*theta[l,d])^2), from the differences, accumulated in the
+ *   order d = 0..dim-1 (r*theta[l,d] rounded first, as the notebook's `theta * r`).
+ *   slice_sum (pairs*slices) out : S_l = sum_i |key_s(i) - key_t(i)|^p over the sorted keys.
+ *   coef_s / coef_t (pairs*slices*n) scratch, both NULL for a value-only call : (d S_l / d key) / key in original
+ *   point order, 0 where key == 0 -- a point exactly at r theta contributes gradient 0 where the notebook's autograd
+ *   yields NaN (the one deliberate deviation).  The two backward entries read them:
+ *   grad_x[b,i,:]      = sum_l slice_w[b,l] * coef[b,l,i] * (x[b,i,:] - r theta[b,l,:])
+ *   grad_thetas[b,l,:] = -r slice_w[b,l] * sum_i ( coef_s[b,l,i] * (xs[b,i,:] - r theta[b,l,:])
+ *                                                + coef_t[b,l,i] * (xt[b,i,:] - r theta[b,l,:]) ),
+ *   grad_xs / grad_xt (pairs, n, dim); grad_thetas always (pairs, slices, dim) -- directions shared by several pairs
+ *   sum their rows on the host side.  pairs <= 65535 in the backward entries (pairs ride on gridDim.y).  Gradients
+ *   are reduced in a fixed order (no atomics).
+ * Returns hipErrorInvalidValue on a null pointer, dim outside 1..64, n outside 1..4096, a pair stride shorter than
+ * slices*dim, p < 1 or pairs over the limit. */
+SHW_API int shw_gsw_circular_forward(const float* xs, const float* xt, const float* thetas, int pairs, int n, int dim,
+                                     int slices, long theta_pair_stride, float r, float p, float* slice_sum,
+                                     float* coef_s, float* coef_t, void* stream);
+
+SHW_API int shw_gsw_circular_backward_points(const float* xs, const float* xt, const float* thetas, const float* coef_s,
+                                             const float* coef_t, const float* slice_w, int pairs, int n, int dim,
+                                             int slices, long theta_pair_stride, float r, float* grad_xs,
+                                             float* grad_xt, void* stream);
+
+SHW_API int shw_gsw_circular_backward_dirs(const float* xs, const float* xt, const float* thetas, const float* coef_s,
+                                           const float* coef_t, const float* slice_w, int pairs, int n, int dim,
+                                           int slices, long theta_pair_stride, float r, float* grad_thetas,
+                                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Log-domain Sinkhorn distance (comparison metric); value-only entry point.
  * Replaces: log_Sinkhorn_Distance_Loss.forward and log_N_Sinkhorn_Distance_Loss.forward
  * (/root/reference/Comparison_Wasserstein_with_Chamfer_distance/losses/sinkhorn.py:14-63, :104-157), called at

@@ -94,6 +94,19 @@ _SIGNATURES = {
                                                    ctypes.c_void_p]),
     "shw_esw_backward_dirs_dim": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_f32p, ctypes.c_void_p]),
+    # generalised sliced-W (csrc/shw_gsw.hip): rows of caller-computed keys, and the fused circular defining function
+    "shw_gsw_rows_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_float, _c_f32p,
+                                            _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_gsw_circular_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_float, _c_f32p,
+                                                _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_gsw_circular_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                        ctypes.c_long, ctypes.c_float, _c_f32p, _c_f32p,
+                                                        ctypes.c_void_p]),
+    "shw_gsw_circular_backward_dirs": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_long, ctypes.c_float, _c_f32p, ctypes.c_void_p]),
     "shw_sinkhorn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "shw_sinkhorn_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
