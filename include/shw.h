@@ -436,6 +436,37 @@ SHW_API int shw_sinkhorn_backward(const float* x, const float* y, int pairs, int
                                   int norm_p, int cost_pow, void* workspace, const float* grad_cost, float* grad_x,
                                   float* grad_y, void* stream);
 
+/* The same backward for a loss that also consumes the plan P and the cost matrix C of shw_sinkhorn_forward_train
+ * (the reference's P and C are autograd-visible, sinkhorn.py:46-60).  Additive, ABI 3.
+ *   grad_cost (pairs), grad_plan (pairs, n, m), grad_cost_matrix (pairs, n, m) in : upstream gradients of cost, P and C;
+ *   each may be NULL (= zero).  With Ghat_ij = g C_ij + GP_ij the recursion starts from
+ *     ubar_i = sum_j P_ij Ghat_ij / eps,  vbar_j = sum_i P_ij Ghat_ij / eps,
+ *     K_ij = P_ij (g (1 - C_ij / eps) - GP_ij / eps) + GC_ij,  gx_i = sum_j K_ij dC_ij/dx_i,  gy_j = sum_i K_ij dC_ij/dy_j
+ *   and then walks the iterations exactly as shw_sinkhorn_backward does.  The two dense tensors are read once per side
+ *   (x side: one wave per row, lanes along j; y side: one thread per column); no atomics, deterministic.
+ *   With grad_plan = grad_cost_matrix = NULL the result equals shw_sinkhorn_backward's up to rounding (not bit for bit:
+ *   callers that need the bits call that entry). */
+SHW_API int shw_sinkhorn_backward_plan(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter,
+                                       int norm_p, int cost_pow, void* workspace, const float* grad_cost,
+                                       const float* grad_plan, const float* grad_cost_matrix, float* grad_x, float* grad_y,
+                                       void* stream);
+
+/* Soft correspondences without dense tensors: the barycentric map of the plan, from the same single solve as the cost.
+ *   map (pairs, n, 3) out : T_i = sum_j P_ij y_j / r_i;  row_sum (pairs, n) out : r_i = sum_j P_ij;  cost (pairs) out as
+ *   shw_sinkhorn_forward_train (same bits).  A row whose whole sum underflowed (r_i = 0) gets T_i = 0 and passes no gradient.
+ *   workspace : shw_sinkhorn_train_workspace_bytes(pairs, n, m, max_iter), passed unchanged to shw_sinkhorn_map_backward.
+ * shw_sinkhorn_map_backward: grad_map (pairs, n, 3) in, grad_cost (pairs) in or NULL; grad_x, grad_y out (overwritten).
+ *   It is shw_sinkhorn_backward_plan with the implicit rank-3 cotangent GP_ij = G_i . (y_j - T_i) / r_i, GC = 0, and the
+ *   direct term gy_j += sum_i P_ij G_i / r_i; nothing (pairs, n, m) is read or written. */
+SHW_API int shw_sinkhorn_map_forward(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter,
+                                     int norm_p, int cost_pow, float thresh, void* workspace, float* cost, float* map,
+                                     float* row_sum, void* stream);
+
+SHW_API int shw_sinkhorn_map_backward(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter,
+                                      int norm_p, int cost_pow, void* workspace, const float* map, const float* row_sum,
+                                      const float* grad_map, const float* grad_cost, float* grad_x, float* grad_y,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Chamfer distance (comparison baseline).
  * Replaces: pytorch3d.loss.chamfer_distance with default arguments, as called at

@@ -118,6 +118,16 @@ _SIGNATURES = {
     "shw_sinkhorn_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_f32p, _c_f32p,
                                              _c_f32p, ctypes.c_void_p]),
+    # gradients through the plan and the cost matrix (dense cotangents, each may be null), and the barycentric map
+    "shw_sinkhorn_backward_plan": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_f32p, _c_f32p,
+                                                  _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_sinkhorn_map_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
+                                                _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_sinkhorn_map_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_f32p, _c_f32p,
+                                                 _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_chamfer_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_f32p,
                                            ctypes.c_void_p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_void_p]),
     "shw_chamfer_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p,

@@ -13,7 +13,9 @@
 // chunk), and the convergence test is a device-side flag that turns the remaining launches into no-ops, so
 // the whole solve is enqueued without a host round trip.  K = 3: no MFMA; the passes are VALU +
 // transcendental bound.  Round 2: the backward through the unrolled iterations (shw_sinkhorn_forward_train /
-// shw_sinkhorn_backward below).
+// shw_sinkhorn_backward below).  Round 16: the same backward seeded by cotangents of the plan P and the cost matrix C
+// (shw_sinkhorn_backward_plan) and the barycentric map of the plan without dense tensors (shw_sinkhorn_map_forward /
+// shw_sinkhorn_map_backward).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -426,6 +428,254 @@ __global__ __launch_bounds__(256) void sinkhorn_bwd_y_kernel(SinkBwdArgs A, int 
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Seeds of the same recursion for a loss that also consumes the plan P and the cost matrix C (the reference's are
+// autograd-visible, sinkhorn.py:46-60).  With upstream g_b (cost), GP_ij (P), GC_ij (C), missing = 0, and the final duals:
+//   Ghat_ij = g C_ij + GP_ij ;  ubar_i = sum_j P_ij Ghat_ij / eps ;  vbar_j = sum_i P_ij Ghat_ij / eps ;
+//   K_ij = P_ij (g (1 - C_ij/eps) - GP_ij/eps) + GC_ij ;  gx_i = sum_j K_ij dC_ij/dx_i ;  gy_j = sum_i K_ij dC_ij/dy_j ,
+// then sinkhorn_bwd_x_kernel / sinkhorn_bwd_y_kernel from t = T down to 1, unchanged.  Two sources of GP:
+//   dense    : GP, GC are (pairs, n, m) tensors, each read once per side.  The y side (thread j, walking i) reads
+//              GP[b, i, j] with consecutive lanes on consecutive addresses.  The x side gives a row to a WAVE, lanes along
+//              j (one lane per row would stride m between lanes): four per-lane accumulators per row, one fixed-order
+//              wave reduction at the end, no LDS; a wave carries kSeedRows rows so that y_j, v_j are loaded once for them.
+//   implicit : the barycentric map T_i = sum_j P_ij y_j / r_i, r_i = sum_j P_ij, with upstream G_i:
+//              GP_ij = G_i . (y_j - T_i) / r_i, GC = 0, and the direct term gy_j += sum_i P_ij G_i / r_i.  sum_j P_ij GP_ij
+//              is 0 analytically, so the x side leaves it out of ubar.  Nothing (pairs, n, m) is read or written.
+// Every gradient row is owned by one thread or one wave: no atomics, the same bits from run to run.
+// ---------------------------------------------------------------------------------------------
+struct SinkSeedArgs {
+  SinkBwdArgs A;            // here A.gcost may be null: the cost is not consumed, g = 0
+  const float* gplan;       // dense: (pairs, n, m) upstream gradient of P, or null
+  const float* gcmat;       // dense: (pairs, n, m) upstream gradient of C, or null
+  const float* map;         // implicit: (pairs, n, 3) the map T of the forward
+  const float* rsum;        // implicit: (pairs, n) the row sums r
+  const float* gmap;        // implicit: (pairs, n, 3) upstream gradient of T
+};
+
+constexpr int kSeedRows = 4;       // rows per wave of the dense x-side seed: 16 rows per block of four waves
+constexpr int kSeedChunk = 16;     // rows a thread of the dense y-side seed loads ahead (of GP and of GC)
+
+// dense cotangents, rows = x: one wave per kSeedRows rows, lanes along j.  grid (ceil(n / 16), pairs)
+__global__ __launch_bounds__(256) void sinkhorn_seed_plan_x_kernel(SinkSeedArgs S) {
+  const SinkBwdArgs& A = S.A;
+  const int b = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int i0 = (blockIdx.x * 4 + wave) * kSeedRows;
+  if (i0 >= A.n) return;                                       // (no barrier in this kernel)
+  const int T = A.done[1];
+  const float* X = A.x + (long)b * A.n * 3;
+  const float* Y = A.y + (long)b * A.m * 3;
+  const float* U = A.traj_u + ((long)T * A.pairs + b) * A.n;
+  const float* V = A.traj_v + ((long)T * A.pairs + b) * A.m;
+  const float g = A.gcost ? A.gcost[b] : 0.f;
+  float rx[kSeedRows], ry[kSeedRows], rz[kSeedRows], ui[kSeedRows];
+  long row[kSeedRows];
+#pragma unroll
+  for (int r = 0; r < kSeedRows; ++r) {
+    const int ic = min(i0 + r, A.n - 1);                       // rows past the end repeat the last one and are not written
+    rx[r] = X[3 * ic]; ry[r] = X[3 * ic + 1]; rz[r] = X[3 * ic + 2]; ui[r] = U[ic];
+    row[r] = ((long)b * A.n + ic) * A.m;
+  }
+  float acc[kSeedRows] = {}, ax[kSeedRows] = {}, ay[kSeedRows] = {}, az[kSeedRows] = {};
+  for (int j = lane; j < A.m; j += 64) {
+    const float yx = Y[3 * j], yy = Y[3 * j + 1], yz = Y[3 * j + 2], vj = V[j];
+    float gp[kSeedRows], gc[kSeedRows];
+#pragma unroll
+    for (int r = 0; r < kSeedRows; ++r) {
+      gp[r] = S.gplan ? S.gplan[row[r] + j] : 0.f;
+      gc[r] = S.gcmat ? S.gcmat[row[r] + j] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < kSeedRows; ++r) {
+      float hx, hy, hz;
+      const float c = pair_cost_grad<false>(rx[r] - yx, ry[r] - yy, rz[r] - yz, A.norm_p, A.cost_pow, hx, hy, hz);
+      const float P = expf(((ui[r] - c) + vj) * A.inv_eps);
+      acc[r] = fmaf(P, fmaf(g, c, gp[r]), acc[r]);
+      const float k = fmaf(P, g * (1.f - c * A.inv_eps) - gp[r] * A.inv_eps, gc[r]);
+      ax[r] = fmaf(k, hx, ax[r]); ay[r] = fmaf(k, hy, ay[r]); az[r] = fmaf(k, hz, az[r]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < kSeedRows; ++r) {
+    const float sa = wave_sum(acc[r], lane), sx = wave_sum(ax[r], lane), sy = wave_sum(ay[r], lane), sz = wave_sum(az[r], lane);
+    if (lane == 0 && i0 + r < A.n) {
+      A.ubar[(long)b * A.n + i0 + r] = sa * A.inv_eps;
+      float* G = A.gx + ((long)b * A.n + i0 + r) * 3;
+      G[0] = sx; G[1] = sy; G[2] = sz;
+    }
+  }
+}
+
+// the map's implicit cotangent, rows = x: one thread per row, as sinkhorn_bwd_cost_kernel.  grid (ceil(n / 256), pairs)
+__global__ __launch_bounds__(256) void sinkhorn_seed_map_x_kernel(SinkSeedArgs S) {
+  __shared__ float4 tile[kSkTile];
+  const SinkBwdArgs& A = S.A;
+  const int b = blockIdx.y;
+  const int T = A.done[1];
+  const float* X = A.x + (long)b * A.n * 3;
+  const float* Y = A.y + (long)b * A.m * 3;
+  const float* U = A.traj_u + ((long)T * A.pairs + b) * A.n;
+  const float* V = A.traj_v + ((long)T * A.pairs + b) * A.m;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int ic = min(i, A.n - 1);
+  const long ri = (long)b * A.n + ic;
+  const float rx = X[3 * ic], ry = X[3 * ic + 1], rz = X[3 * ic + 2], ui = U[ic];
+  const float tx = S.map[3 * ri], ty = S.map[3 * ri + 1], tz = S.map[3 * ri + 2];
+  const float rs = S.rsum[ri];
+  const float inv_r = rs > 0.f ? 1.f / rs : 0.f;               // a row whose sum underflowed passes no gradient
+  const float gax = S.gmap[3 * ri] * inv_r, gay = S.gmap[3 * ri + 1] * inv_r, gaz = S.gmap[3 * ri + 2] * inv_r;
+  const float g = A.gcost ? A.gcost[b] : 0.f;
+  float acc = 0.f, ax = 0.f, ay = 0.f, az = 0.f;
+  for (int base = 0; base < A.m; base += kSkTile) {
+    const int cnt = min(kSkTile, A.m - base);
+    __syncthreads();
+    for (int t = threadIdx.x; t < cnt; t += 256) {
+      const int j = base + t;
+      tile[t] = make_float4(Y[3 * j], Y[3 * j + 1], Y[3 * j + 2], V[j]);
+    }
+    __syncthreads();
+    for (int t = 0; t < cnt; ++t) {
+      const float4 q = tile[t];
+      float hx, hy, hz;
+      const float c = pair_cost_grad<false>(rx - q.x, ry - q.y, rz - q.z, A.norm_p, A.cost_pow, hx, hy, hz);
+      const float P = expf(((ui - c) + q.w) * A.inv_eps);
+      const float gp = fmaf(gax, q.x - tx, fmaf(gay, q.y - ty, gaz * (q.z - tz)));      // G_i . (y_j - T_i) / r_i
+      acc = fmaf(P, c, acc);
+      const float k = P * (g * (1.f - c * A.inv_eps) - gp * A.inv_eps);
+      ax = fmaf(k, hx, ax); ay = fmaf(k, hy, ay); az = fmaf(k, hz, az);
+    }
+  }
+  if (i < A.n) {
+    A.ubar[ri] = g * acc * A.inv_eps;
+    float* G = A.gx + ri * 3;
+    G[0] = ax; G[1] = ay; G[2] = az;
+  }
+}
+
+// rows = y, both sources: thread j walks i through LDS tiles of (x_i, u_i); DENSE reads GP[b, i, j], GC[b, i, j] (coalesced
+// along j), the implicit form stages (G_i / r_i, G_i . T_i / r_i) as a second float4.  grid (ceil(m / 256), pairs)
+template <bool DENSE>
+__global__ __launch_bounds__(256) void sinkhorn_seed_y_kernel(SinkSeedArgs S) {
+  __shared__ float4 tile[kSkTile];
+  __shared__ float4 tile2[DENSE ? 1 : kSkTile];
+  const SinkBwdArgs& A = S.A;
+  const int b = blockIdx.y;
+  const int T = A.done[1];
+  const float* X = A.x + (long)b * A.n * 3;
+  const float* Y = A.y + (long)b * A.m * 3;
+  const float* U = A.traj_u + ((long)T * A.pairs + b) * A.n;
+  const float* V = A.traj_v + ((long)T * A.pairs + b) * A.m;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  const int jc = min(j, A.m - 1);                              // threads past the end repeat the last column, unwritten
+  const float rx = Y[3 * jc], ry = Y[3 * jc + 1], rz = Y[3 * jc + 2], vj = V[jc];
+  const float g = A.gcost ? A.gcost[b] : 0.f;
+  float s = 0.f, ax = 0.f, ay = 0.f, az = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
+  for (int base = 0; base < A.n; base += kSkTile) {
+    const int cnt = min(kSkTile, A.n - base);
+    __syncthreads();
+    for (int q = threadIdx.x; q < cnt; q += 256) {
+      const int i = base + q;
+      tile[q] = make_float4(X[3 * i], X[3 * i + 1], X[3 * i + 2], U[i]);
+      if constexpr (!DENSE) {
+        const long ri = (long)b * A.n + i;
+        const float rs = S.rsum[ri];
+        const float inv_r = rs > 0.f ? 1.f / rs : 0.f;
+        const float gax = S.gmap[3 * ri] * inv_r, gay = S.gmap[3 * ri + 1] * inv_r, gaz = S.gmap[3 * ri + 2] * inv_r;
+        tile2[q] = make_float4(gax, gay, gaz, fmaf(gax, S.map[3 * ri], fmaf(gay, S.map[3 * ri + 1], gaz * S.map[3 * ri + 2])));
+      }
+    }
+    __syncthreads();
+    const long col = ((long)b * A.n + base) * A.m + jc;
+    auto term = [&](int q, float gp, float gc) {
+      const float4 c4 = tile[q];
+      float hx, hy, hz;                                         // d = y - x: the derivative w.r.t. the row point y_j
+      const float c = pair_cost_grad<false>(rx - c4.x, ry - c4.y, rz - c4.z, A.norm_p, A.cost_pow, hx, hy, hz);
+      const float P = expf(((c4.w - c) + vj) * A.inv_eps);
+      if constexpr (!DENSE) {
+        const float4 e = tile2[q];
+        gp = fmaf(e.x, rx, fmaf(e.y, ry, e.z * rz)) - e.w;      // G_i . (y_j - T_i) / r_i
+        dx = fmaf(P, e.x, dx); dy = fmaf(P, e.y, dy); dz = fmaf(P, e.z, dz);         // the direct term sum_i P_ij G_i / r_i
+      }
+      s = fmaf(P, fmaf(g, c, gp), s);
+      const float k = fmaf(P, g * (1.f - c * A.inv_eps) - gp * A.inv_eps, gc);
+      ax = fmaf(k, hx, ax); ay = fmaf(k, hy, ay); az = fmaf(k, hz, az);
+    };
+    int q = 0;
+    if constexpr (DENSE) {
+      // a column is walked by one thread, so what keeps HBM busy is the loads a thread has in flight: 2 x kSeedChunk
+      for (; q + kSeedChunk <= cnt; q += kSeedChunk) {
+        float gp[kSeedChunk], gc[kSeedChunk];
+#pragma unroll
+        for (int k = 0; k < kSeedChunk; ++k) {
+          gp[k] = S.gplan ? S.gplan[col + (long)(q + k) * A.m] : 0.f;
+          gc[k] = S.gcmat ? S.gcmat[col + (long)(q + k) * A.m] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < kSeedChunk; ++k) term(q + k, gp[k], gc[k]);
+      }
+      for (; q < cnt; ++q)
+        term(q, S.gplan ? S.gplan[col + (long)q * A.m] : 0.f, S.gcmat ? S.gcmat[col + (long)q * A.m] : 0.f);
+    } else {
+      for (; q < cnt; ++q) term(q, 0.f, 0.f);
+    }
+  }
+  if (j < A.m) {
+    A.vbar[(long)b * A.m + j] = s * A.inv_eps;
+    float* G = A.gy + ((long)b * A.m + j) * 3;
+    G[0] = ax + dx; G[1] = ay + dy; G[2] = az + dz;
+  }
+}
+
+// training forward of the map: sinkhorn_cost_traj_kernel (the same sums for the cost, in the same order) that also writes
+// T_i = sum_j P_ij y_j / r_i and r_i = sum_j P_ij; a row whose sum underflowed to 0 gets T_i = 0
+__global__ __launch_bounds__(256) void sinkhorn_map_traj_kernel(const float* x, const float* y, const float* tu, const float* tv,
+                                                                const int* done, int pairs, int n, int m, float inv_eps,
+                                                                int norm_p, int cost_pow, float* __restrict__ partial,
+                                                                float* __restrict__ map, float* __restrict__ rsum) {
+  __shared__ float4 tile[kSkTile];
+  __shared__ float red[4];
+  const int b = blockIdx.y;
+  const int T = done[1];
+  const float* X = x + (long)b * n * 3;
+  const float* Y = y + (long)b * m * 3;
+  const float* U = tu + ((long)T * pairs + b) * n;
+  const float* V = tv + ((long)T * pairs + b) * m;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int ic = min(i, n - 1);
+  const float rx = X[3 * ic], ry = X[3 * ic + 1], rz = X[3 * ic + 2], ui = U[ic];
+  float acc = 0.f, rs = 0.f, tx = 0.f, ty = 0.f, tz = 0.f;
+  for (int base = 0; base < m; base += kSkTile) {
+    const int cnt = min(kSkTile, m - base);
+    __syncthreads();
+    for (int t = threadIdx.x; t < cnt; t += 256) {
+      const int j = base + t;
+      tile[t] = make_float4(Y[3 * j], Y[3 * j + 1], Y[3 * j + 2], V[j]);
+    }
+    __syncthreads();
+    for (int t = 0; t < cnt; ++t) {
+      const float4 q = tile[t];
+      const float c = pair_cost<false>(rx - q.x, ry - q.y, rz - q.z, norm_p, cost_pow);
+      const float p = expf(((ui - c) + q.w) * inv_eps);
+      if (i < n) {
+        acc = fmaf(p, c, acc);
+        rs += p;
+        tx = fmaf(p, q.x, tx); ty = fmaf(p, q.y, ty); tz = fmaf(p, q.z, tz);
+      }
+    }
+  }
+  if (i < n) {
+    const long ri = (long)b * n + i;
+    const float inv_r = rs > 0.f ? 1.f / rs : 0.f;
+    rsum[ri] = rs;
+    map[3 * ri] = tx * inv_r; map[3 * ri + 1] = ty * inv_r; map[3 * ri + 2] = tz * inv_r;
+  }
+  acc = wave_sum(acc, threadIdx.x & 63);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[(long)b * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 }  // namespace shw
 
 extern "C" {
@@ -490,14 +740,9 @@ static void sink_train_layout(void* workspace, int pairs, int n, int m, int max_
   done = (int*)(partial + (size_t)pairs * blocks);
 }
 
-int shw_sinkhorn_forward_train(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter,
-                               int norm_p, int cost_pow, float thresh, void* workspace, float* cost, float* plan,
-                               float* cost_matrix, void* stream) {
-  if (!x || !y || !workspace || !cost) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || pairs > 65535 || n < 1 || m < 1 || !(eps > 0.f) || max_iter < 0 || norm_p < 1 || cost_pow < 1)
-    return (int)hipErrorInvalidValue;
-  if (pairs == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
+// the training iterations: slot 0 of both trajectories = 0, then max_iter sweeps that each write the next slot
+static int sink_train_iterate(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter, int norm_p,
+                              int cost_pow, float thresh, void* workspace, hipStream_t st) {
   const size_t blocks = (size_t)(n + 255) / 256;
   float *tu, *tv, *ubar, *vbar, *err, *partial;
   int* done;
@@ -522,11 +767,63 @@ int shw_sinkhorn_forward_train(const float* x, const float* y, int pairs, int n,
     }
     hipLaunchKernelGGL(shw::sinkhorn_check_kernel, dim3(1), dim3(64), 0, st, err, done, pairs, thresh);
   }
+  return 0;
+}
+
+int shw_sinkhorn_forward_train(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter,
+                               int norm_p, int cost_pow, float thresh, void* workspace, float* cost, float* plan,
+                               float* cost_matrix, void* stream) {
+  if (!x || !y || !workspace || !cost) return (int)hipErrorInvalidValue;
+  if (pairs < 0 || pairs > 65535 || n < 1 || m < 1 || !(eps > 0.f) || max_iter < 0 || norm_p < 1 || cost_pow < 1)
+    return (int)hipErrorInvalidValue;
+  if (pairs == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t blocks = (size_t)(n + 255) / 256;
+  float *tu, *tv, *ubar, *vbar, *err, *partial;
+  int* done;
+  sink_train_layout(workspace, pairs, n, m, max_iter, tu, tv, ubar, vbar, err, partial, done);
+  const int rc = sink_train_iterate(x, y, pairs, n, m, eps, max_iter, norm_p, cost_pow, thresh, workspace, st);
+  if (rc) return rc;
   // the value: cost kernel on the last EXECUTED slot (device-side count)
-  hipLaunchKernelGGL(shw::sinkhorn_cost_traj_kernel, grid_u, dim3(256), 0, st, x, y, tu, tv, done, pairs, n, m, 1.f / eps,
-                     norm_p, cost_pow, partial, plan, cost_matrix);
+  hipLaunchKernelGGL(shw::sinkhorn_cost_traj_kernel, dim3((n + 255) / 256, pairs), dim3(256), 0, st, x, y, tu, tv, done, pairs,
+                     n, m, 1.f / eps, norm_p, cost_pow, partial, plan, cost_matrix);
   hipLaunchKernelGGL(shw::sinkhorn_cost_reduce_kernel, dim3(pairs), dim3(64), 0, st, partial, (int)blocks, cost);
   return (int)hipGetLastError();
+}
+
+int shw_sinkhorn_map_forward(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter, int norm_p,
+                             int cost_pow, float thresh, void* workspace, float* cost, float* map, float* row_sum,
+                             void* stream) {
+  if (!x || !y || !workspace || !cost || !map || !row_sum) return (int)hipErrorInvalidValue;
+  if (pairs < 0 || pairs > 65535 || n < 1 || m < 1 || !(eps > 0.f) || max_iter < 0 || norm_p < 1 || cost_pow < 1)
+    return (int)hipErrorInvalidValue;
+  if (pairs == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t blocks = (size_t)(n + 255) / 256;
+  float *tu, *tv, *ubar, *vbar, *err, *partial;
+  int* done;
+  sink_train_layout(workspace, pairs, n, m, max_iter, tu, tv, ubar, vbar, err, partial, done);
+  const int rc = sink_train_iterate(x, y, pairs, n, m, eps, max_iter, norm_p, cost_pow, thresh, workspace, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(shw::sinkhorn_map_traj_kernel, dim3((n + 255) / 256, pairs), dim3(256), 0, st, x, y, tu, tv, done, pairs,
+                     n, m, 1.f / eps, norm_p, cost_pow, partial, map, row_sum);
+  hipLaunchKernelGGL(shw::sinkhorn_cost_reduce_kernel, dim3(pairs), dim3(64), 0, st, partial, (int)blocks, cost);
+  return (int)hipGetLastError();
+}
+
+// the walk over the iterations, t = max_iter .. 1, after a seed pair has written ubar, vbar, grad_x, grad_y
+static void sink_bwd_walk(const shw::SinkBwdArgs& A, int max_iter, hipStream_t st) {
+  const dim3 grid_x((A.n + 255) / 256, A.pairs), grid_y((A.m + 255) / 256, A.pairs);
+  const bool fast = A.norm_p == 2 && A.cost_pow == 1;
+  for (int t = max_iter; t >= 1; --t) {
+    if (fast) {
+      hipLaunchKernelGGL((shw::sinkhorn_bwd_x_kernel<true>), grid_x, dim3(256), 0, st, A, t);
+      hipLaunchKernelGGL((shw::sinkhorn_bwd_y_kernel<true>), grid_y, dim3(256), 0, st, A, t);
+    } else {
+      hipLaunchKernelGGL((shw::sinkhorn_bwd_x_kernel<false>), grid_x, dim3(256), 0, st, A, t);
+      hipLaunchKernelGGL((shw::sinkhorn_bwd_y_kernel<false>), grid_y, dim3(256), 0, st, A, t);
+    }
+  }
 }
 
 int shw_sinkhorn_backward(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter, int norm_p,
@@ -550,15 +847,46 @@ int shw_sinkhorn_backward(const float* x, const float* y, int pairs, int n, int 
     hipLaunchKernelGGL((shw::sinkhorn_bwd_cost_kernel<true, false>), grid_x, dim3(256), 0, st, A);
     hipLaunchKernelGGL((shw::sinkhorn_bwd_cost_kernel<false, false>), grid_y, dim3(256), 0, st, A);
   }
-  for (int t = max_iter; t >= 1; --t) {
-    if (fast) {
-      hipLaunchKernelGGL((shw::sinkhorn_bwd_x_kernel<true>), grid_x, dim3(256), 0, st, A, t);
-      hipLaunchKernelGGL((shw::sinkhorn_bwd_y_kernel<true>), grid_y, dim3(256), 0, st, A, t);
-    } else {
-      hipLaunchKernelGGL((shw::sinkhorn_bwd_x_kernel<false>), grid_x, dim3(256), 0, st, A, t);
-      hipLaunchKernelGGL((shw::sinkhorn_bwd_y_kernel<false>), grid_y, dim3(256), 0, st, A, t);
-    }
-  }
+  sink_bwd_walk(A, max_iter, st);
+  return (int)hipGetLastError();
+}
+
+int shw_sinkhorn_backward_plan(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter, int norm_p,
+                               int cost_pow, void* workspace, const float* grad_cost, const float* grad_plan,
+                               const float* grad_cost_matrix, float* grad_x, float* grad_y, void* stream) {
+  if (!x || !y || !workspace || !grad_x || !grad_y) return (int)hipErrorInvalidValue;
+  if (pairs < 0 || pairs > 65535 || n < 1 || m < 1 || !(eps > 0.f) || max_iter < 0 || norm_p < 1 || cost_pow < 1)
+    return (int)hipErrorInvalidValue;
+  if (pairs == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  float *tu, *tv, *ubar, *vbar, *err, *partial;
+  int* done;
+  sink_train_layout(workspace, pairs, n, m, max_iter, tu, tv, ubar, vbar, err, partial, done);
+  shw::SinkBwdArgs A{x, y, tu, tv, done, ubar, vbar, grad_x, grad_y, grad_cost, pairs, n, m, eps, 1.f / eps, norm_p, cost_pow};
+  shw::SinkSeedArgs S{A, grad_plan, grad_cost_matrix, nullptr, nullptr, nullptr};
+  const int rows_per_block = 4 * shw::kSeedRows;
+  hipLaunchKernelGGL(shw::sinkhorn_seed_plan_x_kernel, dim3((n + rows_per_block - 1) / rows_per_block, pairs), dim3(256), 0, st, S);
+  hipLaunchKernelGGL((shw::sinkhorn_seed_y_kernel<true>), dim3((m + 255) / 256, pairs), dim3(256), 0, st, S);
+  sink_bwd_walk(A, max_iter, st);
+  return (int)hipGetLastError();
+}
+
+int shw_sinkhorn_map_backward(const float* x, const float* y, int pairs, int n, int m, float eps, int max_iter, int norm_p,
+                              int cost_pow, void* workspace, const float* map, const float* row_sum, const float* grad_map,
+                              const float* grad_cost, float* grad_x, float* grad_y, void* stream) {
+  if (!x || !y || !workspace || !map || !row_sum || !grad_map || !grad_x || !grad_y) return (int)hipErrorInvalidValue;
+  if (pairs < 0 || pairs > 65535 || n < 1 || m < 1 || !(eps > 0.f) || max_iter < 0 || norm_p < 1 || cost_pow < 1)
+    return (int)hipErrorInvalidValue;
+  if (pairs == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  float *tu, *tv, *ubar, *vbar, *err, *partial;
+  int* done;
+  sink_train_layout(workspace, pairs, n, m, max_iter, tu, tv, ubar, vbar, err, partial, done);
+  shw::SinkBwdArgs A{x, y, tu, tv, done, ubar, vbar, grad_x, grad_y, grad_cost, pairs, n, m, eps, 1.f / eps, norm_p, cost_pow};
+  shw::SinkSeedArgs S{A, nullptr, nullptr, map, row_sum, grad_map};
+  hipLaunchKernelGGL(shw::sinkhorn_seed_map_x_kernel, dim3((n + 255) / 256, pairs), dim3(256), 0, st, S);
+  hipLaunchKernelGGL((shw::sinkhorn_seed_y_kernel<false>), dim3((m + 255) / 256, pairs), dim3(256), 0, st, S);
+  sink_bwd_walk(A, max_iter, st);
   return (int)hipGetLastError();
 }
 

@@ -7,6 +7,8 @@ of an unwritten scratch word shows.
   general solver (uniform weights): equals the equal-size path to 2e-4
   backward                        : finite gradients
   Chamfer / Euclidean SW          : finite
+  Sinkhorn plan (n <= 1024)       : soft map from the dense P (plan_grad=True) vs the fused map kernels, value and both
+                                    gradients to 1e-3 of the largest entry
   float64 (n <= its limit)        : p = 2 slice costs equal to the float32 kernels' to 1e-4 c + 5e-7 sqrt(c) on 99.8 %, shifts on
                                     99 % of the slices, finite double gradients (the gradients themselves are not
                                     compared: float32 decides near-ties of shifts and of coordinates on its own)
@@ -237,6 +239,28 @@ def main(budget=None):
                 e = shw.sliced_wasserstein_distance(x[0], y[0], num_projection=64, p=2, device=dev)
                 if not bool(torch.isfinite(e).all()):
                     problems.append("esw non-finite")
+        if trips % 7 == 3 and n <= 1024:
+            # Sinkhorn through the plan: the soft map from the dense P (plan_grad=True, dense cotangents) and from the
+            # fused kernels (implicit cotangent) are two implementations of one function, value and both gradients
+            Bs = min(B, 2)
+            Gm = torch.randn(Bs, n, 3, generator=gen).to(dev)
+            grads = []
+            for fused in (False, True):
+                xa, ya = x[:Bs].clone().requires_grad_(True), y[:Bs].clone().requires_grad_(True)
+                poison()
+                if fused:
+                    Tm, cost_s = shw.sinkhorn_barycentric_map(xa, ya, 0.5, 5, return_cost=True)
+                else:
+                    cost_s, P, _ = shw.sinkhorn_pair_costs(xa, ya, 0.5, 5, return_plan=True, plan_grad=True)
+                    Tm = P @ ya / P.sum(-1, keepdim=True).clamp_min(1e-38)
+                poison()
+                ((Gm * Tm).sum() + cost_s.sum()).backward()
+                grads.append((Tm.detach(), xa.grad, ya.grad))
+            for name, a_, b_ in zip(("map", "gx", "gy"), *grads):
+                if not bool(torch.isfinite(a_).all() and torch.isfinite(b_).all()):
+                    problems.append(f"sinkhorn plan / map: non-finite {name}")
+                elif float((a_ - b_).abs().max()) > 1e-3 * float(a_.abs().max()) + 1e-6:
+                    problems.append(f"sinkhorn plan vs fused map {name}: max abs {float((a_ - b_).abs().max())}")
         if problems:
             bad += 1
             print("PROBLEM", kind, n, m, B, problems, flush=True)
