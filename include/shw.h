@@ -394,6 +394,57 @@ SHW_API int shw_gsw_circular_backward_dirs(const float* xs, const float* xt, con
                                            void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * 1-D optimal transport on the line (csrc/shw_line_ot.hip): two weighted empirical measures of n and m atoms, n != m
+ * allowed.  cost = W_p^p = int_0^1 |F_u^-1(t) - F_v^-1(t)|^p dt (the quantile merge), mass-normalised: for n == m and
+ * no weights it equals the Euclidean / generalised entries' sum divided by n.  float32, 1 <= n, m <= 4096, p >= 1.
+ * Weights (both forms): a pointer or NULL (uniform) per side, and a stride in floats from one row's (pair's) weights to
+ * the next, 0 = one weight row shared by all; a non-zero stride must be >= the side's count.  Weights are >= 0 and
+ * finite with a positive sum per row; the kernel divides by the sum.  The sign and the sum are NOT checked on the
+ * device: a row whose weights sum to 0 or less yields, in bounded time, a value that means nothing.  A zero weight contributes nothing
+ * and gets coefficient 0.  With both sides NULL the CDFs are the exact integer grid of lcm(n, m) steps.
+ * There is no gradient with respect to the weights.  Cost and coefficients are the same bits on every run.
+ *
+ * Rows of keys the caller computed (any defining function).
+ *   u (rows, n), v (rows, m) contiguous; rows >= 0, any count.
+ *   row_cost (rows) out.
+ *   coef_u (rows, n) / coef_v (rows, m) out, both NULL for a value-only call : d row_cost[r] / d u[r,i] and
+ *   d row_cost[r] / d v[r,j] in original element order: the sum over the merged intervals in which the atom is active of
+ *   delta * p |d|^(p-1) sgn(d), d = u - v (negated for v; 0 at d == 0).
+ * Returns hipErrorInvalidValue on a null pointer (other than weights and both coefficient rows), one coefficient row
+ * without the other, n or m outside 1..4096, rows < 0, p < 1, or a weight stride that is non-zero with a null pointer or
+ * shorter than the count. */
+SHW_API int shw_line_rows_forward(const float* u, const float* v, long rows, int n, int m, float p,
+                                  const float* u_weights, const float* v_weights, long u_weight_stride,
+                                  long v_weight_stride, float* row_cost, float* coef_u, float* coef_v, void* stream);
+
+/* Fused Euclidean projection: xs (pairs, n, dim), xt (pairs, m, dim), 1 <= dim <= 64, pairs <= 65535; thetas
+ * (slices, dim) shared (theta_pair_stride = 0) or (pairs, slices, dim) (stride >= slices*dim).  The key of point i on
+ * slice l is sum_d x[i,d] * theta[l,d] accumulated in the order d = 0..dim-1 (the keys of shw_esw_forward_dim, bit for
+ * bit); no (pairs, slices, n) key matrix is formed.  Weights are per pair: stride 0 or >= the count.
+ *   slice_cost (pairs*slices) out : W_p^p of the two projected measures.
+ *   coef_s (pairs*slices*n) / coef_t (pairs*slices*m) scratch, both NULL for a value-only call : d slice_cost / d key
+ *   in original point order; the two backward entries read them.
+ * Returns hipErrorInvalidValue as the rows form, and on dim outside 1..64, pairs outside 0..65535 or a pair stride
+ * shorter than slices*dim. */
+SHW_API int shw_line_esw_forward(const float* xs, const float* xt, const float* thetas, int pairs, int n, int m, int dim,
+                                 int slices, long theta_pair_stride, float p, const float* u_weights,
+                                 const float* v_weights, long u_weight_stride, long v_weight_stride, float* slice_cost,
+                                 float* coef_s, float* coef_t, void* stream);
+
+/* grad_xs[b,i,:] = sum_l slice_w[b,l] * coef_s[b,l,i] * theta[b,l,:] (pairs, n, dim), and grad_xt (pairs, m, dim) from
+ * coef_t; slices summed in the order l = 0..slices-1.  Same limits as the forward entry. */
+SHW_API int shw_line_esw_backward_points(const float* thetas, const float* coef_s, const float* coef_t,
+                                         const float* slice_w, int pairs, int n, int m, int dim, int slices,
+                                         long theta_pair_stride, float* grad_xs, float* grad_xt, void* stream);
+
+/* grad_thetas[b,l,:] = slice_w[b,l] * ( sum_i coef_s[b,l,i] * xs[b,i,:] + sum_j coef_t[b,l,j] * xt[b,j,:] ), always
+ * (pairs, slices, dim) -- directions shared by several pairs sum their rows on the host side.  Reduced in a fixed
+ * order (no atomics).  Same limits as the forward entry. */
+SHW_API int shw_line_esw_backward_dirs(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
+                                       const float* slice_w, int pairs, int n, int m, int dim, int slices,
+                                       float* grad_thetas, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Log-domain Sinkhorn distance (comparison metric); value-only entry point.
  * Replaces: log_Sinkhorn_Distance_Loss.forward and log_N_Sinkhorn_Distance_Loss.forward
  * (/root/reference/Comparison_Wasserstein_with_Chamfer_distance/losses/sinkhorn.py:14-63, :104-157), called at

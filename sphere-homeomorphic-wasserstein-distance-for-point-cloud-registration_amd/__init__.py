@@ -9,6 +9,7 @@ from .esw import (augmented_sliced_wassersten_distance, augmented_sliced_wassers
 from .gsw import (GSWD_circular, GSWD_polynomial, cosine_distance_torch, distributional_sliced_wasserstein_distance,
                   gsw_circular_slice_sums, gsw_nn_1, gsw_nn_3, gsw_polynomial_slice_sums, max_GSWD_circular,
                   max_GSWD_polynomial_3, max_GSWD_polynomial_5, max_gsw_nn_1, max_gsw_nn_3, poly_degree, sorted_row_sums)
+from .line_ot import esw_slice_costs, line_ot_rows, weighted_sliced_wasserstein_distance
 from .modules import (ChamferCriterion, GraphedAscent, GraphedStep, SlicedSphereW, SSWCriterion, max_cos_disimilarity_wassersten_distance,
                       max_spherical_wassersten_distance, max_spherical_wassersten_distance_fast)
 from .sinkhorn import (log_N_Sinkhorn_Distance_Loss, log_Sinkhorn_Distance_Loss, sinkhorn_barycentric_map,
@@ -24,4 +25,5 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "ssw_pair_losses", "GSWD_circular", "GSWD_polynomial", "cosine_distance_torch",
            "distributional_sliced_wasserstein_distance", "gsw_circular_slice_sums", "gsw_nn_1", "gsw_nn_3",
            "gsw_polynomial_slice_sums", "max_GSWD_circular", "max_GSWD_polynomial_3", "max_GSWD_polynomial_5",
-           "max_gsw_nn_1", "max_gsw_nn_3", "poly_degree", "sorted_row_sums"]
+           "max_gsw_nn_1", "max_gsw_nn_3", "poly_degree", "sorted_row_sums", "esw_slice_costs", "line_ot_rows",
+           "weighted_sliced_wasserstein_distance"]

@@ -107,6 +107,18 @@ _SIGNATURES = {
     "shw_gsw_circular_backward_dirs": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
                                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                       ctypes.c_long, ctypes.c_float, _c_f32p, ctypes.c_void_p]),
+    # 1-D optimal transport on the line (csrc/shw_line_ot.hip): unequal sizes and weights, rows of keys or fused projection
+    "shw_line_rows_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                             _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, _c_f32p, _c_f32p, _c_f32p,
+                                             ctypes.c_void_p]),
+    "shw_line_esw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_float, _c_f32p, _c_f32p,
+                                            ctypes.c_long, ctypes.c_long, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_line_esw_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, _c_f32p,
+                                                    _c_f32p, ctypes.c_void_p]),
+    "shw_line_esw_backward_dirs": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_f32p, ctypes.c_void_p]),
     "shw_sinkhorn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "shw_sinkhorn_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
