@@ -60,6 +60,20 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 
   float key[EPT], u[EPT];
   float sum_v = 0.f, sum_u = 0.f;
+  // The full 32-keys-per-lane class takes the rolling loader (ssw_common.hpp): sub-chunks of 8 rows, the next one in
+  // flight while one is computed, and the first one of each cloud issued ahead of the loader -- the source's here, beside
+  // the frame (the addresses do not depend on it), the target's before the source's sort.  `pre` passes through the
+  // `which` loop, so the sort's code is emitted once; 168 VGPRs, 3 waves per SIMD, no spill.
+  constexpr bool ROLL = EPT == 32 && FULL;
+  constexpr int SUB = 8;
+  PointChunk<SUB> pre;
+#ifndef SHW_ABL_NO_COORDS
+  if constexpr (ROLL) {
+    int ln = lane;
+    asm volatile("" : "+v"(ln));
+    if (A.dirs) issue_points<SUB>(A.xs + (long)b * A.n * A.pstride, ln, 0, pre);
+  }
+#endif
 #ifdef SHW_DBG_RUNLEN
   int dbg_run = 0;
 #endif
@@ -81,9 +95,15 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
       part += key[r];
     }
 #else
-    // the full 32-keys-per-lane class loads 16 points per chunk (48 loads in flight per lane): the registers are there
-    // since the sort keeps no per-key words (0.2092 -> 0.2070 ms per step at config 3; the other classes keep 8)
-    const float part = load_coords<EPT, FULL, false, kWave, false, (EPT == 32 && FULL) ? 16 : 8>(X, count, ln, U, key);
+    float part;
+    if constexpr (ROLL) {
+      part = load_coords_rolling<EPT, SUB>(X, ln, U, key, pre);
+      // the target's first rows travel while the source is sorted (which == 0 only: never past the pair's target; rows
+      // of coordinates, dirs == NULL, issue nothing ahead)
+      if (which == 0 && A.dirs) issue_points<SUB>(A.xt + (long)b * A.m * A.pstride, ln, 0, pre);
+    } else {
+      part = load_coords<EPT, FULL>(X, count, ln, U, key);
+    }
 #endif
 #ifdef SHW_DBG_RUNLEN          // developer build (tools/nonuniform_time.py): slice_shift reports the longest equal-bin run
     if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL>(key, ln, count, scratch, A.dirs == nullptr));

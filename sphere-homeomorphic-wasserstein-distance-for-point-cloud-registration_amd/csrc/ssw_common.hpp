@@ -666,8 +666,7 @@ __device__ __forceinline__ int solve_shift_ext(const float (&u)[EPT], const floa
 // NCOL: lanes that share the cloud (64 for one wave; 64*W when W waves of a workgroup own a slice together, `lane`
 // then being the index among those lanes): lane owns points r*NCOL + lane.
 // FOLD: how the masked classes take coordinate-row mode, see below.
-// MOST: most points per lane whose loads are issued together (the chunk of the projection loop).
-template <int EPT, bool FULL = false, bool CHAINED = false, int NCOL = kWave, bool FOLD = false, int MOST = 8>
+template <int EPT, bool FULL = false, bool CHAINED = false, int NCOL = kWave, bool FOLD = false>
 __device__ __forceinline__ float load_coords(const float* __restrict__ X, int count, int lane,
                                              const float (&U)[6], float (&key)[EPT], int live_count = -1) {
   // `count` bounds the addresses (clamp), `live_count` (default: count) says how many of the 64*EPT slots are
@@ -697,7 +696,7 @@ __device__ __forceinline__ float load_coords(const float* __restrict__ X, int co
   }
   const int wide = (kFold && rows) ? 0 : -1;       // all ones: 12-byte records
   const int o1 = (kFold && rows) ? 0 : 1, o2 = (kFold && rows) ? 0 : 2;
-  constexpr int CH = chunk_of(EPT, MOST);          // 8 points (24 loads) in flight per lane (4 or 5 for the odd classes)
+  constexpr int CH = chunk_of(EPT);                // 8 points (24 loads) in flight per lane (4 or 5 for the odd classes)
 #pragma unroll
   for (int r0 = 0; r0 < EPT; r0 += CH) {
     if constexpr (!FULL && !kFold) {
@@ -771,6 +770,60 @@ __device__ __forceinline__ float load_coords(const float* __restrict__ X, int co
       }
     }
     __builtin_amdgcn_sched_barrier(0);
+  }
+  return acc;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Rolling loader of a full class (the 2048-point one-wave loss kernel): the cloud's rows go through the projection in
+// sub-chunks of SUB rows, and the loads of sub-chunk c + 1 are issued before the arithmetic of sub-chunk c, so the wave
+// waits for a partial count (s_waitcnt vmcnt(SUB)) with the next records already on their way, where load_coords drains
+// the queue once per chunk.  The FIRST sub-chunk is issued by the caller (issue_points), as early as it knows the cloud:
+// the source's beside the frame, the target's before the source's sort.  The addresses are those of load_coords' full
+// path -- rows r0 .. r0 + SUB - 1 of the cloud X, each once, r0 < EPT -- and the coordinates, the order of `acc` and the
+// keys are its values bit for bit.  Rows of coordinates (U[0] NaN) take load_coords' own branch: nothing is issued ahead.
+// ---------------------------------------------------------------------------------------------
+template <int SUB>
+struct PointChunk {
+  float x[SUB], y[SUB], z[SUB];
+};
+
+// issue the loads of rows [r0, r0 + SUB) of a full cloud: lane owns points r * 64 + lane (scalar base, one unsigned
+// offset per lane, the row in the immediate field: see load_coords)
+template <int SUB>
+__device__ __forceinline__ void issue_points(const float* __restrict__ X, int lane, int r0, PointChunk<SUB>& P) {
+  const size_t o3 = (size_t)(3u * (unsigned)lane);
+#pragma unroll
+  for (int j = 0; j < SUB; ++j) {
+    const float* row = X + 3 * (r0 + j) * kWave;
+    P.x[j] = row[o3]; P.y[j] = row[o3 + 1]; P.z[j] = row[o3 + 2];
+  }
+}
+
+template <int EPT, int SUB>
+__device__ __forceinline__ float load_coords_rolling(const float* __restrict__ X, int lane, const float (&U)[6],
+                                                     float (&key)[EPT], const PointChunk<SUB>& first) {
+  static_assert(EPT % SUB == 0, "whole sub-chunks");
+  if (U[0] != U[0]) return load_coords<EPT, true>(X, EPT * kWave, lane, U, key);
+  float acc = 0.f;
+  PointChunk<SUB> cur = first;
+#pragma unroll
+  for (int r0 = 0; r0 < EPT; r0 += SUB) {
+    PointChunk<SUB> nxt;
+    if (r0 + SUB < EPT) {                            // never past the cloud's last row
+      issue_points<SUB>(X, lane, r0 + SUB, nxt);
+      __builtin_amdgcn_sched_barrier(0);             // the loads stay in front of the arithmetic
+    }
+#pragma unroll
+    for (int j = 0; j < SUB; ++j) {
+      const float a = fmaf(cur.z[j], U[4], fmaf(cur.y[j], U[2], fmaf(cur.x[j], U[0], 0.f)));
+      const float b = fmaf(cur.z[j], U[5], fmaf(cur.y[j], U[3], fmaf(cur.x[j], U[1], 0.f)));
+      const float c = circle_coord(a, b);
+      acc += c;
+      key[r0 + j] = c;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (r0 + SUB < EPT) cur = nxt;
   }
   return acc;
 }
