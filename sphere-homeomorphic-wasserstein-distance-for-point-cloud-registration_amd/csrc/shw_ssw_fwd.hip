@@ -43,6 +43,7 @@ template <int EPT, int WAVES, int PMODE, bool FULL>
 __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) void ssw_forward_kernel(SswArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr bool BINS = forward_uses_bins(EPT);
+  constexpr bool GROUPED = shift_fetch_grouped(EPT, WAVES, PMODE, FULL);       // sorted target in groups of four rows
   const int lane = threadIdx.x & 63;
   // (one wave per workgroup: a literal 0 makes the LDS addresses of the sort constants -- the counter of a key is then
   //  ds_add(off) with no base to add)
@@ -118,7 +119,9 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
       for (int r = 0; r < EPT; ++r) u[r] = key[r];
     } else {
       sum_v = wave_sum(part, lane);
-      if constexpr (FULL || !BINS) {
+      if constexpr (GROUPED) {
+        write_grouped_rows<EPT>(vbuf, lane, key);
+      } else if constexpr (FULL || !BINS) {
 #pragma unroll
         for (int r = 0; r < EPT; ++r) vbuf[r * kWave + lane] = key[r];
       }
@@ -133,7 +136,7 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 #else
   int k;
   if constexpr (FULL || !BINS) {
-    k = solve_shift<EPT, PMODE, FULL, true>(u, vbuf, lane, A.n, sum_u, sum_v, A.p, A.p_int, best);
+    k = solve_shift<EPT, PMODE, FULL, true, GROUPED>(u, vbuf, lane, A.n, sum_u, sum_v, A.p, A.p_int, best);
   } else {
     // any n: pre-rotated extended rows over the sort's scratch (counters + staging buffer are dead), target kept in
     // registers for the rare rewrite

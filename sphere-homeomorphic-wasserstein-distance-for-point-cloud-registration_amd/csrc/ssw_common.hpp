@@ -447,10 +447,175 @@ __device__ __forceinline__ float shift_cost1_full(const float (&u)[NR], const fl
   return wave_sum_uniform(s, lane & 63);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The fast form again, with the sorted target fetched four rows at a time (n == 64*EPT, one wave, all EPT registers).
+//
+// Layout ("grouped rows"): rows 4g .. 4g + 3 of column col lie side by side, 16 bytes at byte offset g * 1024 + col * 16
+// of the same 256 EPT bytes (16-byte aligned: the target row starts 128 EPT bytes into a 16-byte-aligned block, and a
+// wave's block is 384 EPT bytes).  Consecutive window positions of a lane are consecutive rows of one column until the row
+// index wraps, and a group aligned to 4 never straddles the wrap (4 divides EPT): with a = kl mod 4 and q0 = kl div 4 the
+// window rows kl, kl + 1, ... lie in the aligned groups G = q0 + t, t = 0, 1, ...; group G is group G mod (EPT / 4) of the
+// column with carry G div (EPT / 4).  One select of the address, one of the turn and one add of the wave-uniform group
+// offset then serve four values from one ds_read_b128, where shift_costs3_full pays them per value; the turn is added to
+// every value as before.  Window value j is element (a + j) mod 4 of group (a + j) div 4: a is wave-uniform and a
+// template parameter of the unrolled body, which the caller picks with a scalar branch -- four copies of each body.
+// The values, the order in which every per-lane sum takes them and the reductions are those of shift_costs3_full /
+// shift_cost1_full: every result has the same bits.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGroupRows = 4;
+// Is the sorted target of ssw_forward_kernel<EPT, 1, PMODE, FULL> laid out in grouped rows?  Asked by the kernel that
+// writes it and by the solve that reads it.  The headline class only: the general-power kernel (PMODE 0) spends its time
+// in the powers, not in the fetch, and four copies of its loop bodies would be four times the kernel's largest block; the
+// smaller full one-wave classes are not what the dispatch rule selects (dispatch.hpp: two waves per slice there).
+constexpr bool shift_fetch_grouped(int ept, int waves, int pmode, bool full) {
+  return full && waves == 1 && ept == 32 && pmode == 2;
+}
+
+// lane's sorted keys (rows 0 .. EPT - 1 of column `lane`) into the grouped layout: EPT / 4 ds_write_b128
+template <int EPT>
+__device__ __forceinline__ void write_grouped_rows(float* vbuf, int lane, const float (&key)[EPT]) {
+  char* col = reinterpret_cast<char*>(vbuf) + lane * (4 * kGroupRows);
+#pragma unroll
+  for (int g = 0; g < EPT / kGroupRows; ++g)
+    *reinterpret_cast<float4*>(col + g * (256 * kGroupRows)) =
+        make_float4(key[4 * g], key[4 * g + 1], key[4 * g + 2], key[4 * g + 3]);
+}
+
+// one group: the (address, turn) pair by value, as in inc_fetch
+__device__ __forceinline__ void read_group(const char* at, float turn, float (&out)[kGroupRows]) {
+  const float4 v = *reinterpret_cast<const float4*>(at);
+  out[0] = v.x + turn; out[1] = v.y + turn; out[2] = v.z + turn; out[3] = v.w + turn;
+}
+
+// the three per-lane sums of shift_costs3_full for a window that starts at element A of group q0 of the column with
+// carry 0 (a0, t0); a1, t1 / a2, t2: the columns with carry 1 / 2
+template <int EPT, int PMODE, int A>
+__device__ __forceinline__ void shift_sums3_grouped(const float (&u)[EPT], const char* rows, int a0, int a1, int a2,
+                                                    float t0, float t1, float t2, int q0, float p, int p_int,
+                                                    float& sm, float& s0, float& sp) {
+  constexpr int GW = kGroupRows;
+  constexpr int GPC = EPT / GW;                                 // groups per column
+  constexpr int NG = (A + EPT + 1) / GW + 1;                    // groups that hold the EPT + 2 window values: 9 or 10
+  float grp[NG][GW];
+  auto load = [&](int t) {                                      // t compile-time after unrolling
+    const int G = q0 + t;                                       // scalar; t < GPC: carry 0 or 1, else 1 or 2
+    const bool carry = (t < GPC) ? (G >= GPC) : (G >= 2 * GPC);
+    const int a = (t < GPC) ? (carry ? a1 : a0) : (carry ? a2 : a1);
+    const float tn = (t < GPC) ? (carry ? t1 : t0) : (carry ? t2 : t1);
+    read_group(rows + a + (G & (GPC - 1)) * (256 * GW), tn, grp[t]);
+  };
+  // group t is first needed by window value max(0, 4 t - A); a chunk of eight rows fetches the groups that begin among
+  // its eight new window values
+#pragma unroll
+  for (int t = 0; t < NG; ++t) if (GW * t - A <= 1) load(t);
+  sm = 0.f; s0 = 0.f; sp = 0.f;
+  float prev = grp[A / GW][A % GW], cur = grp[(A + 1) / GW][(A + 1) % GW];
+  constexpr int CH = 8;
+#pragma unroll
+  for (int r0 = 0; r0 < EPT; r0 += CH) {
+#pragma unroll
+    for (int t = 0; t < NG; ++t) if (GW * t - A >= r0 + 2 && GW * t - A <= r0 + CH + 1) load(t);
+#pragma unroll
+    for (int j = 0; j < CH; ++j) {
+      const float nxt = grp[(A + r0 + j + 2) / GW][(A + r0 + j + 2) % GW];
+      sm += pow_abs<PMODE>(u[r0 + j] - prev, p, p_int);
+      s0 += pow_abs<PMODE>(u[r0 + j] - cur, p, p_int);
+      sp += pow_abs<PMODE>(u[r0 + j] - nxt, p, p_int);
+      prev = cur;
+      cur = nxt;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// shift_costs3_full on grouped rows
+template <int EPT, int PMODE>
+__device__ __forceinline__ void shift_costs3_grouped(const float (&u)[EPT], const float* vbuf, int lane, int k, float p,
+                                                     int p_int, float& cm, float& c0, float& cp) {
+  static_assert(EPT % 8 == 0, "whole groups, chunks of eight rows");
+  constexpr int LOG = __builtin_ctz(EPT);
+  const int base = k - 1;
+  const int kl = base & (EPT - 1);
+  const int kh = base >> LOG;                                   // floor division (arithmetic shift)
+  int addr[3];
+  float turn[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int col = lane + kh + c;                              // unwrapped lane index of the atom
+    addr[c] = (col & 63) << 4;                                  // byte offset of the column inside a row of groups
+    turn[c] = (float)(col >> 6);                                // whole turns around the circle
+  }
+  const char* rows = reinterpret_cast<const char*>(vbuf);
+  const int a = kl & 3, q0 = kl >> 2;                           // scalar
+  float sm, s0, sp;
+  if (a == 0) shift_sums3_grouped<EPT, PMODE, 0>(u, rows, addr[0], addr[1], addr[2], turn[0], turn[1], turn[2], q0, p, p_int, sm, s0, sp);
+  else if (a == 1) shift_sums3_grouped<EPT, PMODE, 1>(u, rows, addr[0], addr[1], addr[2], turn[0], turn[1], turn[2], q0, p, p_int, sm, s0, sp);
+  else if (a == 2) shift_sums3_grouped<EPT, PMODE, 2>(u, rows, addr[0], addr[1], addr[2], turn[0], turn[1], turn[2], q0, p, p_int, sm, s0, sp);
+  else shift_sums3_grouped<EPT, PMODE, 3>(u, rows, addr[0], addr[1], addr[2], turn[0], turn[1], turn[2], q0, p, p_int, sm, s0, sp);
+  cm = wave_sum_uniform(sm, lane & 63);
+  c0 = wave_sum_uniform(s0, lane & 63);
+  cp = wave_sum_uniform(sp, lane & 63);
+}
+
+// the per-lane sum of shift_cost1_full for a window of EPT values that starts at element A of group q0 (carry 0 or 1)
+template <int EPT, int PMODE, int A>
+__device__ __forceinline__ float shift_sum1_grouped(const float (&u)[EPT], const char* rows, int a0, int a1, float t0,
+                                                    float t1, int q0, float p, int p_int) {
+  constexpr int GW = kGroupRows;
+  constexpr int GPC = EPT / GW;
+  constexpr int NG = (A + EPT - 1) / GW + 1;                    // 8 or 9
+  float grp[NG][GW];
+  auto load = [&](int t) {                                      // t compile-time after unrolling
+    const int G = q0 + t;                                       // scalar, below 2 GPC
+    const bool carry = G >= GPC;
+    read_group(rows + (carry ? a1 : a0) + (G & (GPC - 1)) * (256 * GW), carry ? t1 : t0, grp[t]);
+  };
+  float s = 0.f;
+  constexpr int CH = 8;
+#pragma unroll
+  for (int r0 = 0; r0 < EPT; r0 += CH) {
+#pragma unroll
+    for (int t = 0; t < NG; ++t) {
+      const int first = GW * t - A < 0 ? 0 : GW * t - A;        // the window value that needs group t first
+      if (first >= r0 && first < r0 + CH) load(t);
+    }
+#pragma unroll
+    for (int j = 0; j < CH; ++j) s += pow_abs<PMODE>(u[r0 + j] - grp[(A + r0 + j) / GW][(A + r0 + j) % GW], p, p_int);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  return s;
+}
+
+// shift_cost1_full on grouped rows
+template <int EPT, int PMODE>
+__device__ __forceinline__ float shift_cost1_grouped(const float (&u)[EPT], const float* vbuf, int lane, int kk, float p,
+                                                     int p_int) {
+  constexpr int LOG = __builtin_ctz(EPT);
+  const int kl = kk & (EPT - 1);
+  const int kh = kk >> LOG;
+  int addr[2];
+  float turn[2];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = lane + kh + c;
+    addr[c] = (col & 63) << 4;
+    turn[c] = (float)(col >> 6);
+  }
+  const char* rows = reinterpret_cast<const char*>(vbuf);
+  const int a = kl & 3, q0 = kl >> 2;                           // scalar
+  float s;
+  if (a == 0) s = shift_sum1_grouped<EPT, PMODE, 0>(u, rows, addr[0], addr[1], turn[0], turn[1], q0, p, p_int);
+  else if (a == 1) s = shift_sum1_grouped<EPT, PMODE, 1>(u, rows, addr[0], addr[1], turn[0], turn[1], q0, p, p_int);
+  else if (a == 2) s = shift_sum1_grouped<EPT, PMODE, 2>(u, rows, addr[0], addr[1], turn[0], turn[1], q0, p, p_int);
+  else s = shift_sum1_grouped<EPT, PMODE, 3>(u, rows, addr[0], addr[1], turn[0], turn[1], q0, p, p_int);
+  return wave_sum_uniform(s, lane & 63);
+}
+
 // Minimise the convex sequence c(k), |k| <= n (theta in [-1, 1], the reference's bracket :174-177).
 // Returns k*, writes c(k*) (sum form).
 // REUSE: evaluate only the new shift after a unit step (the loss kernel; the training kernels keep three per step).
-template <int EPT, int PMODE, bool FULL = false, bool REUSE = false>
+// GROUPED: the caller wrote the target in grouped rows (shift_fetch_grouped), not in plain ones.
+template <int EPT, int PMODE, bool FULL = false, bool REUSE = false, bool GROUPED = false>
 __device__ __forceinline__ int solve_shift(const float (&u)[EPT], const float* vbuf, int lane, int n,
                                            float sum_u, float sum_v, float p, int p_int, float& best) {
   int lo = -n, hi = n;
@@ -473,10 +638,13 @@ __device__ __forceinline__ int solve_shift(const float (&u)[EPT], const float* v
     const int d = k - kprev;             // wave-uniform
     if (kReuse && (d == 1 || d == -1)) {
       float c;
-      if constexpr (FULL) c = shift_cost1_full<EPT, PMODE>(u, vbuf, ln, k + d, p, p_int);
+      if constexpr (FULL && GROUPED) c = shift_cost1_grouped<EPT, PMODE>(u, vbuf, ln, k + d, p, p_int);
+      else if constexpr (FULL) c = shift_cost1_full<EPT, PMODE>(u, vbuf, ln, k + d, p, p_int);
       else c = shift_cost1<EPT, PMODE>(u, vbuf, ln, n, k + d, p, p_int);
       if (d == 1) { cm = c0; c0 = cp; cp = c; }
       else { cp = c0; c0 = cm; cm = c; }
+    } else if constexpr (FULL && GROUPED) {
+      shift_costs3_grouped<EPT, PMODE>(u, vbuf, ln, k, p, p_int, cm, c0, cp);
     } else if constexpr (FULL) {
       shift_costs3_full<EPT, PMODE>(u, vbuf, ln, k, p, p_int, cm, c0, cp);
     } else if constexpr (SHW_SOLVE_INC && EPT <= 16) {
