@@ -540,6 +540,45 @@ SHW_API int shw_chamfer_backward(const float* x, const float* y, const int32_t* 
                          const float* w, int pairs, int n, int m,
                          float* grad_x, float* grad_y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact Wasserstein cost between two uniform clouds of EQUAL size (csrc/shw_emd.hip).
+ * Replaces: ot.emd2 (POT, a CPU network simplex in a Python loop over the batch) as the reference's live loss calls it:
+ * losses/s2_wasserstein.py:13-66 Cos_disimilarity_W (train_W_COS.py:393, train_Pseudo_W_COS.py:391), :73-126
+ * Geodesic_distance_W, Flow_cube.ipynb cell 5 wasserstein_distance / wasserstein_distance_geo, the W2 metric of the flow
+ * notebooks and main_rotation.py:213-219.  With n = m and uniform weights the problem is a linear assignment problem;
+ * it is solved by an eps-scaling forward auction on fixed-point costs, one workgroup per pair.
+ *   "Exact" means: the returned permutation sigma has mean_i C(i, sigma(i)) <= optimum + K 2^-25, K the power of two
+ *   the kernel finds above the largest cost of the pair -- below the float32 resolution of the costs themselves.
+ *   POT is third-party and not installed: parity with ot.emd2 itself is unpinned; the tests compare with scipy's
+ *   linear_sum_assignment.
+ *   kind 0: C = sum_d |x_d - y_d|^p (cos_cost_matrix, :52-63);  kind 1: C = angle(x, y)^p (geodesic_cost_matrix,
+ *   :112-123) with the angle from atan2(|x cross y|, x . y) and pi / 2 for a zero-length point.  p >= 1, any float.
+ */
+
+/* Largest n of the entries below (2048). */
+SHW_API int shw_max_points_emd(void);
+
+/* Bytes of the workspace the forward writes and the backward reads: the assignment, its inverse, one flag per pair. */
+SHW_API size_t shw_emd_workspace_bytes(int pairs, int n);
+
+/* x, y (pairs, n, 3) fp32;  n == m, 1 <= n <= the limit, pairs <= 65535, pairs == 0 is a no-op.
+ *   cost (pairs) fp32 out  : mean_i C(x_i, y_assign[i]), summed in a fixed order
+ *   assign (pairs, n) int32 out : the target of each source point
+ *   rounds (pairs) int32 out : bidding rounds used.  Every loop is bounded: a pair that would need more than
+ *     1024 n + 4096 rounds (8 x the worst ratio the CPU restatement records) gets cost NaN, rounds = that cap
+ *     and the identity assignment.
+ * Deterministic: the same inputs give the same bits. */
+SHW_API int shw_emd_forward(const float* x, const float* y, int pairs, int n, int m, int kind, float p, void* workspace,
+                            float* cost, int32_t* assign, int32_t* rounds, void* stream);
+
+/* grad of sum_b w[b] cost[b] (w: device pointer, (pairs)); workspace: as the forward left it.  The plan is locally
+ * constant: grad_x[i] = (w/n) dC(x_i, y_assign[i])/dx_i and grad_y[j] likewise through the inverse permutation -- what
+ * ot.emd2's autograd gives through C.  Owner-computed, no atomics, bit-identical from run to run; outputs overwritten.
+ * kind 1: where sin(angle) = 0 or a point has zero length, 0 is written (the reference's acos gives inf / NaN).
+ * A pair whose cost is NaN (round cap) gets zero gradients. */
+SHW_API int shw_emd_backward(const float* x, const float* y, const void* workspace, const float* w, int pairs, int n,
+                             int kind, float p, float* grad_x, float* grad_y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,14 @@ _SIGNATURES = {
     "shw_chamfer_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _c_f32p,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_f32p, _c_f32p,
                                             ctypes.c_void_p]),
+    # exact W for equal-size uniform clouds (csrc/shw_emd.hip): fixed-point auction, one workgroup per pair
+    "shw_max_points_emd": (ctypes.c_int, []),
+    "shw_emd_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "shw_emd_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_float, ctypes.c_void_p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_void_p]),
+    "shw_emd_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -239,8 +239,9 @@ class max_spherical_wassersten_distance_fast(max_spherical_wassersten_distance):
 class max_cos_disimilarity_wassersten_distance(nn.Module):
     """The criterion train_W_COS.py:404 builds (s2_wasserstein.py:211-262): `criteria(template, transformed_source,
     train_or_test=...) -> (cswd, phi(template), phi(source))`.  Same constructor arguments; `CSW` is any
-    `CSW(x, y) -> scalar` module -- the reference passes its exact-EMD `Cos_disimilarity_W` (POT, out of scope),
-    the drop-in passes `SlicedSphereW`.  The s2_wasserstein module itself cannot be imported without POT, so this
+    `CSW(x, y) -> scalar` module -- the reference passes its exact-EMD `Cos_disimilarity_W(device, p=2)`, and so can
+    the caller here (emd.py: the same loss on the device, equal cloud sizes up to 2048 points); `SlicedSphereW` is the
+    sliced surrogate for the same slot.  The s2_wasserstein module itself cannot be imported without POT, so this
     mirror is checked against a restatement (oracle/phi_max_mirror.py): parity unpinned by fixtures."""
 
     def __init__(self, phi, CSW, device, phi_op, max_iter=10, lam=0.1, psi_minibatch_size=5, graph=False):
