@@ -301,6 +301,39 @@ SHW_API int shw_ssw_backward_points_dim(const float* xs, const float* xt, const 
                                         float* grad_xs, float* grad_xt, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Spherical sliced-Wasserstein: gradients with respect to the slicing frames (additive to ABI 3; kernels of
+ * csrc/shw_ssw_dirs.hip).  The coefficient rows every training-form forward writes (coef[b,l,i] = d cost(b,l) /
+ * d coord[b,l,i], original point order) folded with d coord / d U instead of d coord / d x.  With (a_, b_) = U_l^T x_i,
+ * r2 = a_^2 + b_^2 and coord = (atan2(-b_, -a_) + pi) / (2 pi):
+ *   grad_dirs[b,l,:,0] = sc_b sum_i coef[b,l,i] (-b_i) / (2 pi r2_i) x_i
+ *   grad_dirs[b,l,:,1] = sc_b sum_i coef[b,l,i] ( a_i) / (2 pi r2_i) x_i,    sc_b = scale (pair_w[b] + total_w[0]),
+ * summed over the points of both clouds (coef_s with xs, coef_t with xt); a point with r2 == 0 adds 0, the guard of the
+ * point-gradient entries.  pair_w / total_w as in shw_ssw_backward_points (NULL terms count as 0, both NULL = 1).
+ *   grad_dirs (pairs, slices, dim, 2) out, ALWAYS one row per (pair, slice) -- the convention of shw_esw_backward_dirs:
+ *   frames shared by several pairs (u_pair_stride = 0) sum their rows over the pairs on the host side.
+ * The cost does not change when the frame is rotated in its plane or scaled, so every row satisfies
+ *   <g[:,0], u2> - <g[:,1], u1> = 0   and   <g[:,0], u1> + <g[:,1], u2> = 0   up to rounding.
+ * Limits: 1 <= n, m <= shw_max_points() (float32), the larger of shw_max_points_f64() and
+ * shw_max_points_f64_general() (float64, one entry for both float64 paths: n != m allowed); 2 <= dim <= 64.  A null
+ * pointer or a size outside the limits returns 1 without touching the device; pairs == 0 or slices == 0 is a no-op.
+ * More than 65535 pairs go out as several launches.  Sums run in a fixed order without atomics: the same bits on
+ * every run.
+ */
+SHW_API int shw_ssw_backward_dirs(const float* xs, const float* xt, const float* dirs, const float* coef_s,
+                                  const float* coef_t, int pairs, int n, int m, int slices, long u_pair_stride,
+                                  float scale, const float* pair_w, const float* total_w, float* grad_dirs, void* stream);
+
+SHW_API int shw_ssw_backward_dirs_dim(const float* xs, const float* xt, const float* dirs, const float* coef_s,
+                                      const float* coef_t, int pairs, int n, int m, int dim, int slices,
+                                      long u_pair_stride, float scale, const float* pair_w, const float* total_w,
+                                      float* grad_dirs, void* stream);
+
+SHW_API int shw_ssw_backward_dirs_f64(const double* xs, const double* xt, const double* dirs, const double* coef_s,
+                                      const double* coef_t, int pairs, int n, int m, int slices, long u_pair_stride,
+                                      double scale, const double* pair_w, const double* total_w, double* grad_dirs,
+                                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Euclidean sliced-Wasserstein (the notebooks' SWD baseline).
  * Replaces: sliced_wasserstein_distance (Wasserstein_flow_problem/Flow_cube.ipynb:280-292): projection on unit
  * directions, per-slice sort of both projected sequences, sum of |sorted difference|^p.

@@ -17,14 +17,14 @@ from .modules import (ChamferCriterion, GraphedAscent, GraphedStep, SlicedSphere
 from .sinkhorn import (log_N_Sinkhorn_Distance_Loss, log_Sinkhorn_Distance_Loss, sinkhorn_barycentric_map,
                        sinkhorn_pair_costs)
 from .ssw import (binary_search_circle, circle_coordinates, draw_directions, emd1D_circle, enable_float64, enable_float64_general, float64_enabled,
-                  float64_general_enabled, max_points_f64, max_points_f64_general, stiefel_frames, sliced_cost, sliced_wasserstein_sphere, sliced_wasserstein_sphere_fast,
+                  float64_general_enabled, max_points_f64, max_points_f64_general, max_sliced_wasserstein_sphere, retract_frames, stiefel_frames, sliced_cost, sliced_wasserstein_sphere, sliced_wasserstein_sphere_fast,
                   ssw_pair_losses)
 
 __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_circle", "enable_float64", "enable_float64_general", "float64_enabled", "float64_general_enabled", "max_points_f64",
            "max_points_f64_general", "ChamferCriterion", "GraphedAscent", "GraphedStep", "SlicedSphereW", "SSWCriterion",
            "max_spherical_wassersten_distance", "max_spherical_wassersten_distance_fast",
            "max_cos_disimilarity_wassersten_distance", "chamfer_distance", "chamfer_pair_losses", "draw_directions", "log_N_Sinkhorn_Distance_Loss", "log_Sinkhorn_Distance_Loss", "sinkhorn_barycentric_map", "sinkhorn_pair_costs", "stiefel_frames", "augmented_sliced_wassersten_distance", "augmented_sliced_wasserstein_distance", "esw_slice_sums", "rand_projections", "sliced_wasserstein_distance", "sliced_cost", "sliced_wasserstein_sphere", "sliced_wasserstein_sphere_fast",
-           "ssw_pair_losses", "GSWD_circular", "GSWD_polynomial", "cosine_distance_torch",
+           "ssw_pair_losses", "max_sliced_wasserstein_sphere", "retract_frames", "GSWD_circular", "GSWD_polynomial", "cosine_distance_torch",
            "distributional_sliced_wasserstein_distance", "gsw_circular_slice_sums", "gsw_nn_1", "gsw_nn_3",
            "gsw_polynomial_slice_sums", "max_GSWD_circular", "max_GSWD_polynomial_3", "max_GSWD_polynomial_5",
            "max_gsw_nn_1", "max_gsw_nn_3", "poly_degree", "sorted_row_sums", "esw_slice_costs", "line_ot_rows",

@@ -80,6 +80,16 @@ _SIGNATURES = {
                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                                    ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
                                                    ctypes.c_void_p]),
+    # gradients with respect to the slicing frames (csrc/shw_ssw_dirs.hip): the coefficient rows folded with d coord / d U
+    "shw_ssw_backward_dirs": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_float, _c_f32p, _c_f32p,
+                                             _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_backward_dirs_dim": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_float,
+                                                 _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_ssw_backward_dirs_f64": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_double, _c_f32p,
+                                                 _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
                                        ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_esw_backward_points": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,

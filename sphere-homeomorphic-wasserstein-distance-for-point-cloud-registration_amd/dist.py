@@ -65,7 +65,11 @@ def sharded_pair_losses(Xs, Xt, Us, p=2, mode="pairs", group=None, sync_input_gr
     """Replicated inputs Xs (B,n,3), Xt (B,m,3), Us (B,L,3,2) or (L,3,2) on every rank -> (B,) per-pair losses
     on every rank, identical to the single-process result.
 
-    `local_fn(Xs, Xt, Us, p) -> (b,)` evaluates the mean over the given slices for the given pairs."""
+    `local_fn(Xs, Xt, Us, p) -> (b,)` evaluates the mean over the given slices for the given pairs.
+
+    Frames that require grad: each rank's `Us.grad` holds the contribution of its own shard only (the rows of its pairs
+    or slices; for shared frames the sum over its pairs).  `sync_input_grads` covers the clouds, not the frames: frames
+    shared across ranks need the caller's own all-reduce of `Us.grad`."""
     if local_fn is None:
         local_fn = _default_local_fn
     if not dist.is_initialized():

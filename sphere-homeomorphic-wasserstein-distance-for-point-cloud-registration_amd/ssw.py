@@ -366,10 +366,10 @@ class _PairLosses(torch.autograd.Function):
         ws = ctx.lease.ws
         B, n, m, L, stride = ctx.dims
         dev = Xs_c.device
-        gxs = torch.empty_like(Xs_c)
-        gxt = torch.empty_like(Xt_c)
         if g_pair is None and g_total is None and g_first is None:
             return (None,) * 9
+        want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_dirs = ctx.needs_input_grad[2]
         # the upstream gradients go to the kernel as they are: row b is scaled by g_pair[b] + g_total[0] there
         dtype = Xs_c.dtype
         gp = g_pair.to(dtype).contiguous() if g_pair is not None else None
@@ -380,16 +380,30 @@ class _PairLosses(torch.autograd.Function):
                 gp = gp.clone() if gp is not None else torch.zeros(B, dtype=dtype, device=dev)
                 gp[0] += g_first.to(dtype)
         gt = g_total.to(dtype).contiguous() if g_total is not None else None
-        name = ("shw_ssw_backward_points" if dtype == torch.float32 else
-                "shw_ssw_backward_points_general_f64" if ws.slice_cut is not None else "shw_ssw_backward_points_f64")
-        entry = getattr(lib, name)
+        gp_ptr = gp.data_ptr() if gp is not None else None
+        gt_ptr = gt.data_ptr() if gt is not None else None
+        gxs = gxt = gU = None
         with torch.cuda.device(dev):
-            _lib.check(entry(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
-                             ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
-                             1.0 / L, gp.data_ptr() if gp is not None else None,
-                             gt.data_ptr() if gt is not None else None, gxs.data_ptr(),
-                             gxt.data_ptr(), _stream_ptr(dev)), name)
-        return gxs, gxt, None, None, None, None, None, None, None
+            if want_points:
+                gxs = torch.empty_like(Xs_c)
+                gxt = torch.empty_like(Xt_c)
+                name = ("shw_ssw_backward_points" if dtype == torch.float32 else
+                        "shw_ssw_backward_points_general_f64" if ws.slice_cut is not None else
+                        "shw_ssw_backward_points_f64")
+                _lib.check(getattr(lib, name)(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
+                                              ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
+                                              1.0 / L, gp_ptr, gt_ptr, gxs.data_ptr(), gxt.data_ptr(),
+                                              _stream_ptr(dev)), name)
+            if want_dirs:
+                # the same coefficient rows folded with d coord / d U: one row per (pair, slice), shared frames sum theirs
+                gU = torch.empty(B, L, 3, 2, dtype=dtype, device=dev)
+                name = "shw_ssw_backward_dirs" if dtype == torch.float32 else "shw_ssw_backward_dirs_f64"
+                _lib.check(getattr(lib, name)(Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(),
+                                              ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, L, stride,
+                                              1.0 / L, gp_ptr, gt_ptr, gU.data_ptr(), _stream_ptr(dev)), name)
+                if stride == 0:
+                    gU = gU.sum(0)
+        return gxs, gxt, gU, None, None, None, None, None, None
 
 
 class _PairLossesDim(torch.autograd.Function):
@@ -450,8 +464,8 @@ class _PairLossesDim(torch.autograd.Function):
         dev = Xs_c.device
         if g_pair is None and g_total is None and g_first is None:
             return (None,) * 9
-        gxs = torch.empty_like(Xs_c)
-        gxt = torch.empty_like(Xt_c)
+        want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        want_dirs = ctx.needs_input_grad[2]
         gp = g_pair.to(torch.float32).contiguous() if g_pair is not None else None
         if g_first is not None:                     # gradient of the 0-dim first-pair output: belongs to row 0
             if gp is None and B == 1:
@@ -460,13 +474,26 @@ class _PairLossesDim(torch.autograd.Function):
                 gp = gp.clone() if gp is not None else torch.zeros(B, dtype=torch.float32, device=dev)
                 gp[0] += g_first.to(torch.float32)
         gt = g_total.to(torch.float32).contiguous() if g_total is not None else None
+        gp_ptr = gp.data_ptr() if gp is not None else None
+        gt_ptr = gt.data_ptr() if gt is not None else None
+        gxs = gxt = gU = None
         with torch.cuda.device(dev):
-            _lib.check(lib.shw_ssw_backward_points_dim(
-                Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m, d,
-                L, stride, 1.0 / L, gp.data_ptr() if gp is not None else None,
-                gt.data_ptr() if gt is not None else None, gxs.data_ptr(), gxt.data_ptr(), _stream_ptr(dev)),
-                "shw_ssw_backward_points_dim")
-        return gxs, gxt, None, None, None, None, None, None, None
+            if want_points:
+                gxs = torch.empty_like(Xs_c)
+                gxt = torch.empty_like(Xt_c)
+                _lib.check(lib.shw_ssw_backward_points_dim(
+                    Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m,
+                    d, L, stride, 1.0 / L, gp_ptr, gt_ptr, gxs.data_ptr(), gxt.data_ptr(), _stream_ptr(dev)),
+                    "shw_ssw_backward_points_dim")
+            if want_dirs:
+                gU = torch.empty(B, L, d, 2, dtype=torch.float32, device=dev)
+                _lib.check(lib.shw_ssw_backward_dirs_dim(
+                    Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), ws.coef_s.data_ptr(), ws.coef_t.data_ptr(), B, n, m,
+                    d, L, stride, 1.0 / L, gp_ptr, gt_ptr, gU.data_ptr(), _stream_ptr(dev)),
+                    "shw_ssw_backward_dirs_dim")
+                if stride == 0:
+                    gU = gU.sum(0)
+        return gxs, gxt, gU, None, None, None, None, None, None
 
 
 def _check_weights(name, w, count, B, dev, dtype=torch.float32):
@@ -492,7 +519,14 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     pairs that the reduction kernel produces in the same launch (the batched reference value, _fast.py:291-293)].
     Scratch (per-slice arrays, gradient coefficients) lives in a pooled SSWWorkspace; results are fresh tensors.
     Losses, per-slice costs and gradients have the input's dtype; float64 with n != m or weights needs
-    `enable_float64_general()` and, like the float32 general path, returns a zero shift tensor with the slices."""
+    `enable_float64_general()` and, like the float32 general path, returns a zero shift tensor with the slices.
+    Differentiable in the two clouds AND in the frames `Us` (every path: R^3 float32, D-generic, both float64 paths):
+    `Us.grad` has the shape of `Us`, shared frames receive the sum over the pairs.  The frame gradient is the derivative of
+    the loss as a function of an arbitrary (d,2) matrix (no projection on the Stiefel tangent space); since the loss does
+    not change when a frame is rotated in its plane or scaled, <g[:,0], u2> = <g[:,1], u1> and <g[:,0], u1> = -<g[:,1], u2>.
+    Backward launches the point-gradient kernel only if a cloud requires grad and the frame-gradient kernel
+    (csrc/shw_ssw_dirs.hip) only if `Us` does; with frames that do not require grad nothing differs from before, and
+    with frames that do, the loss and the point gradients keep their bits.  Weights are not differentiable."""
     _check_sphere_cloud("Xs", Xs)
     _check_sphere_cloud("Xt", Xt)
     _check_cloud_dirs(Us)
@@ -517,10 +551,9 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     wv = _check_weights("v_weights", v_weights, Xt.shape[1], Xs.shape[0], Xs.device, Xs.dtype)
     # evaluation under torch.no_grad() on inputs that still carry requires_grad must not run the
     # training kernel / allocate the coefficient scratch
-    need_grad = torch.is_grad_enabled() and (Xs.requires_grad or Xt.requires_grad)
+    need_grad = torch.is_grad_enabled() and (Xs.requires_grad or Xt.requires_grad or Us.requires_grad)
     op = _PairLosses if d == 3 else _PairLossesDim
-    pair, total, cost, shift, first = op.apply(Xs, Xt, Us.detach(), float(p), shared, wu, wv, need_grad,
-                                               bool(return_slices))
+    pair, total, cost, shift, first = op.apply(Xs, Xt, Us, float(p), shared, wu, wv, need_grad, bool(return_slices))
     if return_first:                                # 0-dim loss of the first pair (the per-pair call shape)
         return first
     if return_total:
@@ -597,6 +630,44 @@ def sliced_wasserstein_sphere_fast(Xs, Xt, num_projections, device, u_weights=No
     """Reference batched signature (_fast.py:298).  Xs (B,n,3), Xt (B,m,3) -> shape-[1] tensor."""
     U = draw_directions(num_projections, device, batch=Xs.shape[0], d=Xs.shape[2], dtype=Xs.dtype)
     return sliced_cost(Xs, Xt, U, p=p, u_weights=u_weights, v_weights=v_weights)
+
+
+def retract_frames(Z):
+    """(..., d, 2) matrices -> orthonormal 2-frames by Gram-Schmidt on the columns: q1 = z1 / |z1|,
+    q2 = (z2 - <z2, q1> q1) / |.|.  The retraction of `max_sliced_wasserstein_sphere`: <q1, z1> = |z1| and
+    <q2, z2> = |z2 - <z2, q1> q1| are never negative, so a column cannot flip its sign as it can in a reduced QR with
+    LAPACK's convention (which would leave Adam's moments pointing the wrong way).  Plain torch on a few small matrices."""
+    z1, z2 = Z[..., 0], Z[..., 1]
+    q1 = z1 / torch.linalg.vector_norm(z1, dim=-1, keepdim=True)
+    r = z2 - (z2 * q1).sum(-1, keepdim=True) * q1
+    q2 = r / torch.linalg.vector_norm(r, dim=-1, keepdim=True)
+    return torch.stack((q1, q2), dim=-1)
+
+
+def max_sliced_wasserstein_sphere(Xs, Xt, num_projections=1, device=None, p=2, max_iter=10, lr=0.05, u_weights=None,
+                                  v_weights=None, return_frames=False):
+    """Max-sliced spherical W: the frames are drawn as `sliced_wasserstein_sphere` / `_fast` draw them
+    (`draw_directions`, the global torch generator), moved by `max_iter` Adam ASCENT steps (step size `lr`) on the loss
+    against the detached clouds -- the frame gradient of `ssw_pair_losses` -- and brought back to the Stiefel manifold
+    after every step by `retract_frames`; then the loss at the final frames, differentiable in the clouds.
+    Xs (n,d), Xt (m,d) -> 0-dim tensor; Xs (B,n,d), Xt (B,m,d) -> shape-[1] tensor (per-pair frames), as `sliced_cost`.
+    `device` None: the clouds' device.  With `return_frames` also the final frames, (L,d,2) resp. (B,L,d,2), detached.
+    The counterpart of `max_sliced_wasserstein_distance` (Euclidean) and `max_GSWD_*` (generalised) for the sphere."""
+    device = Xs.device if device is None else device
+    batch = Xs.shape[0] if Xs.dim() == 3 else None
+    U = draw_directions(num_projections, device, batch=batch, d=Xs.shape[-1], dtype=Xs.dtype).requires_grad_(True)
+    xs_d, xt_d = Xs.detach(), Xt.detach()
+    optimizer = torch.optim.Adam([U], lr=lr)
+    with torch.enable_grad():
+        for _ in range(max_iter):
+            value = sliced_cost(xs_d, xt_d, U, p=p, u_weights=u_weights, v_weights=v_weights)
+            optimizer.zero_grad()
+            (-value.sum()).backward()
+            optimizer.step()
+            U.data = retract_frames(U.data)
+    frames = U.detach()
+    value = sliced_cost(Xs, Xt, frames, p=p, u_weights=u_weights, v_weights=v_weights)
+    return (value, frames) if return_frames else value
 
 
 # ------------------------------------------------------------------------------------------------------------------
