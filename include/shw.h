@@ -574,7 +574,8 @@ SHW_API int shw_chamfer_backward(const float* x, const float* y, const int32_t* 
                          float* grad_x, float* grad_y, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Exact Wasserstein cost between two uniform clouds of EQUAL size (csrc/shw_emd.hip).
+ * Exact Wasserstein cost between two uniform clouds of EQUAL size (csrc/shw_emd.hip); clouds of different sizes:
+ * shw_emd_units_* further down.
  * Replaces: ot.emd2 (POT, a CPU network simplex in a Python loop over the batch) as the reference's live loss calls it:
  * losses/s2_wasserstein.py:13-66 Cos_disimilarity_W (train_W_COS.py:393, train_Pseudo_W_COS.py:391), :73-126
  * Geodesic_distance_W, Flow_cube.ipynb cell 5 wasserstein_distance / wasserstein_distance_geo, the W2 metric of the flow
@@ -611,6 +612,43 @@ SHW_API int shw_emd_forward(const float* x, const float* y, int pairs, int n, in
  * A pair whose cost is NaN (round cap) gets zero gradients. */
 SHW_API int shw_emd_backward(const float* x, const float* y, const void* workspace, const float* w, int pairs, int n,
                              int kind, float p, float* grad_x, float* grad_y, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exact Wasserstein cost between two uniform clouds of DIFFERENT sizes (csrc/shw_emd_units.hip).
+ * Replaces: ot.emd2 where the trainers give the clouds different point counts (train_W_COS.py:292-293, 334-336
+ * --source_p_n / --target_p_n; train_RUNNER.py:193-218: 128 source points against 256 and 512 target points).
+ * With g = gcd(n, m), ks = m / g, kt = n / g, U = lcm(n, m) = n ks = m kt: every source carries ks units of mass 1 / U,
+ * every target has kt slots; supplies and demands are integral in units, so the transport optimum is the optimum of the
+ * U x U assignment problem between units and slots, solved by the rule of shw_emd_forward without expanding the clouds
+ * (a bidding unit evaluates the cost once per target).  "Exact" as above: mean over units <= optimum + K 2^-25.
+ * SIZES.  1 <= n, m <= 2048, U <= 4096 (a bid word names its bidder in 12 bits), and the kernel's LDS footprint
+ * 40 U + 12 (n + m) bytes (each count rounded up to 4) at most 162 816 (the CU's 160 KB less 1 KB): every pair with
+ * lcm(n, m) <= 2048, n == m included, and above that e.g. (768, 1024) and (1024, 1536), U = 3072.  Everything else is
+ * REFUSED: (1000, 1024) has U = 128 000.  Uniform weights only; kind and p as above.
+ */
+
+/* U = lcm(n, m) if the pair is served, else 0.  Makes no HIP call. */
+SHW_API int shw_emd_units_supported(int n, int m);
+
+/* Bytes of the workspace: the target of each unit, the source of each slot (pairs * U int32 each), one flag per pair.
+ * 0 for a pair that is not served. */
+SHW_API size_t shw_emd_units_workspace_bytes(int pairs, int n, int m);
+
+/* x (pairs, n, 3), y (pairs, m, 3) fp32; pairs <= 65535, pairs == 0 is a no-op.
+ *   cost (pairs) fp32 out        : (1/U) sum_q C(x[q / ks], y[targets[q]]), summed in a fixed order
+ *   targets (pairs, U) int32 out : the target POINT (not the slot) of each unit; units i ks .. i ks + ks - 1 belong to
+ *                                  source i, and every target is named by exactly kt units
+ *   rounds (pairs) int32 out     : bidding rounds used; a pair that would need more than 1024 U + 4096 gets cost NaN,
+ *                                  rounds = that cap and unit q on target q / kt.
+ * Deterministic: the same inputs give the same bits.  With n == m, targets is shw_emd_forward's assign. */
+SHW_API int shw_emd_units_forward(const float* x, const float* y, int pairs, int n, int m, int kind, float p,
+                                  void* workspace, float* cost, int32_t* targets, int32_t* rounds, void* stream);
+
+/* grad of sum_b w[b] cost[b]; workspace: as the forward left it.  grad_x[i] = (w/U) sum over the ks units of x_i of
+ * dC(x_i, y_t)/dx_i in unit order, grad_y[j] the same over its kt slots in slot order.  Owner-computed, no atomics,
+ * bit-identical from run to run; outputs overwritten; zero conventions as shw_emd_backward. */
+SHW_API int shw_emd_units_backward(const float* x, const float* y, const void* workspace, const float* w, int pairs, int n,
+                                   int m, int kind, float p, float* grad_x, float* grad_y, void* stream);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,15 @@ _SIGNATURES = {
                                        ctypes.c_void_p]),
     "shw_emd_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    # exact W for uniform clouds of different sizes (csrc/shw_emd_units.hip): the same auction on lcm(n, m) units of mass
+    "shw_emd_units_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "shw_emd_units_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_emd_units_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_float, ctypes.c_void_p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
+    "shw_emd_units_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_f32p, _c_f32p,
+                                              ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

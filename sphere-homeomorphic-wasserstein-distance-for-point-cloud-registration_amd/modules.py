@@ -240,7 +240,8 @@ class max_cos_disimilarity_wassersten_distance(nn.Module):
     """The criterion train_W_COS.py:404 builds (s2_wasserstein.py:211-262): `criteria(template, transformed_source,
     train_or_test=...) -> (cswd, phi(template), phi(source))`.  Same constructor arguments; `CSW` is any
     `CSW(x, y) -> scalar` module -- the reference passes its exact-EMD `Cos_disimilarity_W(device, p=2)`, and so can
-    the caller here (emd.py: the same loss on the device, equal cloud sizes up to 2048 points); `SlicedSphereW` is the
+    the caller here (emd.py: the same loss on the device, up to 2048 points per cloud, equal sizes or the unequal ones of
+    `transport_units`, the runner's 128 against 256 / 512 among them); `SlicedSphereW` is the
     sliced surrogate for the same slot.  The s2_wasserstein module itself cannot be imported without POT, so this
     mirror is checked against a restatement (oracle/phi_max_mirror.py): parity unpinned by fixtures."""
 
