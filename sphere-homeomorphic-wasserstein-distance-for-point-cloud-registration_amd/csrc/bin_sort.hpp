@@ -30,7 +30,12 @@
 // the source-level count); in round 7, in the full classes, the 64 + 31 full-rate v_mov that rotated the loop's
 // registers; since round 8 the full classes' loop runs four phases per trip, which needs no rotation, and exchanges the
 // keys across the lane boundary by two DPP wave shifts instead of two ds_bpermute and two selects: per trip 124 v_min /
-// v_max + 4 v_min / v_max with DPP + 4 v_mov (binsort_read_back_and_fix; profiles/r08_forward_summary.txt).
+// v_max + 4 v_min / v_max with DPP + 4 v_mov (binsort_read_back_and_fix; profiles/r08_forward_summary.txt).  The g mod 4
+// odd phases are straight-line code: behind the loop in rounds 8 - 22, at the price of 16 v_mov_b64 at the loop's exit and
+// 16 / 32 more for a remainder of two / three phases, once per sort, where paths of different length met in different
+// registers; since round 23 the headline loss kernel runs them FIRST, each remainder behind its own copy of the
+// read-back, and pays none of these copies (REM_FIRST; profiles/r23_forward_summary.txt) -- the other full classes keep
+// the earlier order, which costs them fewer registers.
 // With g ~ 9 (uniformly spread coordinates) a quarter of the network's VALU work and an eighth of its crossbar traffic.
 // The result is the exact ascending order of the fp32 keys whatever order the atomics were served in.
 // Data with long runs (clustered clouds, duplicates, an all-zero cloud: g > SHW_BINSORT_MAX_RUN) is detected
@@ -282,35 +287,90 @@ __device__ __forceinline__ void binsort_odd_phase(float (&key)[EPT]) {
   binsort_boundary_dpp<EPT>(key);
 }
 
-// Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition
+// Step 4: read back EPT consecutive positions per lane
 template <int EPT>
-__device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int lane, int g, float* buf) {
-  char* bytes = reinterpret_cast<char*>(buf);
+__device__ __forceinline__ void binsort_read_back(float (&key)[EPT], int lane, const char* bytes) {
 #pragma unroll
   for (int j = 0; j < EPT / 4; ++j) {
     const unsigned pos0 = (unsigned)lane * EPT + 4u * j;          // logical chunk j of row `lane`
     const f32x4 v = *reinterpret_cast<const f32x4*>(bytes + binsort_addr<EPT>(pos0));
     key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
   }
-  // odd-even transposition, g phases: even, odd, even, ... (wave-uniform trip count)
-  // Four phases per trip: a compare-exchange needs a temporary, so the keys leave a phase one register over; after two
-  // phases the compiler copies them back at the loop's back edge (31 v_mov per trip), after four it finds an assignment
-  // that needs no copy.  The last g mod 4 phases are straight-line code behind wave-uniform branches: the keys of paths of
-  // different length meet in different registers, which costs 16 v_mov_b64 at the loop's exit, 16 more for a remainder
-  // of two phases and 32 more for one of three -- once per sort, where the loop of two phases (round 7) paid 31 v_mov per
-  // trip.
-  int phase = 0;
-  for (; phase + 4 <= g; phase += 4) {
-    binsort_even_phase<EPT>(key);
-    binsort_odd_phase<EPT>(key);
-    binsort_even_phase<EPT>(key);
-    binsort_odd_phase<EPT>(key);
-  }
-  if (phase < g) {
-    binsort_even_phase<EPT>(key);
-    if (phase + 1 < g) {
+}
+
+// Steps 4-5: read back EPT consecutive positions per lane, then g phases of odd-even transposition (wave-uniform trip
+// count).  Four phases per loop trip: a compare-exchange needs a temporary, so the keys leave a phase one register over;
+// after two phases the compiler copies them back at the loop's back edge (31 v_mov per trip, round 7), after four it finds
+// an assignment that needs no copy.  Where the g mod 4 odd phases run decides what the paths of different length cost:
+//   * REM_FIRST = false (rounds 8 - 22; every class but the headline's): the loop first, the remainder behind it as
+//     straight-line code behind wave-uniform branches.  The keys of the paths meet in different registers: 16 v_mov_b64 at
+//     the loop's exit, 16 more for a remainder of two phases and 32 more for one of three -- once per sort.
+//   * REM_FIRST = true (round 23; the headline loss kernel): the remainder first -- 1: odd;  2: even, odd;  3: odd, even,
+//     odd -- then the trips, which begin with an even phase, so the alternation is unbroken.  g alternating phases sort a
+//     run of g keys whichever parity comes first (tests/test_fixup_schedule_cpu.py: every 0/1 filling of every run).  Each
+//     remainder has its OWN copy of the read-back (the differing asm comments keep the compiler from merging the four
+//     again): the destinations of the ds_read_b128 are free, so every path is allocated backwards from the registers the
+//     loop header expects, and the loop has one exit.  No copy between the read-back and the loop, none behind the back
+//     edge.  Only where the caller's sorts are straight-line code (the headline kernel's two passes): inside a `which`
+//     loop the same form spills (3 - 5 VGPRs in ssw_forward_kernel<32,1,2,true> and <32,1,0,true>) and costs
+//     ssw_forward_kernel<16,4,2,true> a wave per SIMD (80 -> 84 VGPRs), so those keep the form above.
+template <int EPT, bool REM_FIRST = false>
+__device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int lane, int g, float* buf) {
+  char* bytes = reinterpret_cast<char*>(buf);
+  if constexpr (REM_FIRST) {
+    int ln = lane;
+    switch (g & 3) {
+      case 0:
+        asm volatile("; fix-up remainder 0" : "+v"(ln));
+        binsort_read_back<EPT>(key, ln, bytes);
+        break;
+      case 1:
+        asm volatile("; fix-up remainder 1" : "+v"(ln));
+        binsort_read_back<EPT>(key, ln, bytes);
+        binsort_odd_phase<EPT>(key);
+        break;
+      case 2:
+        asm volatile("; fix-up remainder 2" : "+v"(ln));
+        binsort_read_back<EPT>(key, ln, bytes);
+        binsort_even_phase<EPT>(key);
+        binsort_odd_phase<EPT>(key);
+        break;
+      default:
+        asm volatile("; fix-up remainder 3" : "+v"(ln));
+        binsort_read_back<EPT>(key, ln, bytes);
+        binsort_odd_phase<EPT>(key);
+        binsort_even_phase<EPT>(key);
+        binsort_odd_phase<EPT>(key);
+        break;
+    }
+    for (int trips = g >> 2; trips > 0; --trips) {
+      binsort_even_phase<EPT>(key);
       binsort_odd_phase<EPT>(key);
-      if (phase + 2 < g) binsort_even_phase<EPT>(key);
+      binsort_even_phase<EPT>(key);
+      binsort_odd_phase<EPT>(key);
+    }
+  } else {
+    // (the read-back written out in place: through binsort_read_back the two-wave kernels ssw_forward2_kernel<32,*,true>
+    //  compile to other code, 108 and 128 bytes longer)
+#pragma unroll
+    for (int j = 0; j < EPT / 4; ++j) {
+      const unsigned pos0 = (unsigned)lane * EPT + 4u * j;          // logical chunk j of row `lane`
+      const f32x4 v = *reinterpret_cast<const f32x4*>(bytes + binsort_addr<EPT>(pos0));
+      key[4 * j] = v.x; key[4 * j + 1] = v.y; key[4 * j + 2] = v.z; key[4 * j + 3] = v.w;
+    }
+    int phase = 0;
+    for (; phase + 4 <= g; phase += 4) {
+      binsort_even_phase<EPT>(key);
+      binsort_odd_phase<EPT>(key);
+      binsort_even_phase<EPT>(key);
+      binsort_odd_phase<EPT>(key);
+    }
+    if (phase < g) {
+      binsort_even_phase<EPT>(key);
+      if (phase + 1 < g) {
+        binsort_odd_phase<EPT>(key);
+        if (phase + 2 < g) binsort_even_phase<EPT>(key);
+      }
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -352,7 +412,7 @@ __device__ __forceinline__ int binsort_histogram_full(const float (&key)[EPT], i
 // Steps 3-5 of a full class (only after binsort_histogram_full returned g <= SHW_BINSORT_MAX_RUN).  The byte position of
 // a key is what ds_add_rtn(4) returns on its bin's scanned start (cnt[] holds the bin ends afterwards); inside a bin the
 // keys land in the order the atomics are served, which the fix-up phases make irrelevant.
-template <int EPT>
+template <int EPT, bool REM_FIRST = false>
 __device__ __forceinline__ void binsort_place_full(float (&key)[EPT], const unsigned (&slot)[EPT], int lane, int g,
                                                    float* buf) {
   char* bytes = reinterpret_cast<char*>(buf);
@@ -368,7 +428,7 @@ __device__ __forceinline__ void binsort_place_full(float (&key)[EPT], const unsi
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();
-  binsort_read_back_and_fix<EPT>(key, lane, g, buf);
+  binsort_read_back_and_fix<EPT, REM_FIRST>(key, lane, g, buf);
 }
 
 // ---- the classes with pads (n < 64*EPT): the saturating map, counters in keys -----------------------------------------
@@ -513,7 +573,8 @@ __device__ __forceinline__ void wave_sort_relayout(T (&key)[EPT], int lane, T ma
 // caller-supplied coordinates, not projections) and a key lies outside [0, 1], the domain of the byte-offset map.
 // scratch: binsort_bins<EPT>() counters with the 64*EPT floats of the staging buffer directly behind them (one block).
 // Returns the longest run of keys that share a bin (> SHW_BINSORT_MAX_RUN: the slice took the network).
-template <int EPT, bool FULL>
+// REM_FIRST (full classes): the phase order of binsort_read_back_and_fix.
+template <int EPT, bool FULL, bool REM_FIRST = false>
 __device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* scratch, bool rows) {
   unsigned* cnt = reinterpret_cast<unsigned*>(scratch);
   float* buf = scratch + binsort_bins<EPT>();
@@ -522,7 +583,7 @@ __device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int
     unsigned slot[EPT];
     if (!rows || binsort_keys_fit<EPT>(key)) g = binsort_histogram_full<EPT>(key, lane, cnt, slot);
     if (g <= SHW_BINSORT_MAX_RUN) {
-      binsort_place_full<EPT>(key, slot, lane, g, buf);
+      binsort_place_full<EPT, REM_FIRST>(key, slot, lane, g, buf);
       return g;
     }
   } else {

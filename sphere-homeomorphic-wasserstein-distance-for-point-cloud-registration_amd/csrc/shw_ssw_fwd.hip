@@ -63,8 +63,9 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
   float sum_v = 0.f, sum_u = 0.f;
   // The full 32-keys-per-lane class takes the rolling loader (ssw_common.hpp): sub-chunks of 8 rows, the next one in
   // flight while one is computed, and the first one of each cloud issued ahead of the loader -- the source's here, beside
-  // the frame (the addresses do not depend on it), the target's before the source's sort.  `pre` passes through the
-  // `which` loop, so the sort's code is emitted once; 168 VGPRs, 3 waves per SIMD, no spill.
+  // the frame (the addresses do not depend on it), the target's before the source's sort.  `pre` passes from the
+  // source's pass to the target's (through the `which` loop where it is one: PMODE 0, whose code is emitted once; 168
+  // VGPRs, 3 waves per SIMD, no spill).
   constexpr bool ROLL = EPT == 32 && FULL;
   constexpr int SUB = 8;
   PointChunk<SUB> pre;
@@ -78,7 +79,17 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
 #ifdef SHW_DBG_RUNLEN
   int dbg_run = 0;
 #endif
-#pragma nounroll
+  // TWO_PASS: the headline class runs the source's pass and the target's as straight-line code, one behind the other
+  // (the loop below unrolled by two).  The source's fix-up then leaves its keys in the registers the solve reads as u[]
+  // (inside the loop the sort is emitted once, and the sorted source has to leave the registers the target's sort reuses:
+  // 32 v_mov_b32), the target's feeds write_grouped_rows directly, and the fix-up can run its odd phases first
+  // (bin_sort.hpp, REM_FIRST).  138 VGPRs instead of 168, no spill; the kernel's text grows from 42 268 to 75 312 bytes
+  // (8023 -> 13 904 instructions: 3515 of the added ones are the second copy of the network fallback, about 2400 lie on
+  // the executed path; profiles/r23_forward_summary.txt).  Every other class keeps the loop: the general-power kernel
+  // <32,1,0,true> is 148 KB of text as it is.
+  constexpr bool TWO_PASS = ROLL && PMODE == 2;
+  constexpr int kUnroll = TWO_PASS ? 2 : 1;        // 1: not unrolled
+#pragma unroll kUnroll
   for (int which = 0; which < 2; ++which) {        // 0: source -> registers, 1: target -> LDS
     const float* X = which == 0 ? A.xs + (long)b * A.n * A.pstride : A.xt + (long)b * A.m * A.pstride;
     const int count = which == 0 ? A.n : A.m;
@@ -107,10 +118,10 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
     }
 #endif
 #ifdef SHW_DBG_RUNLEN          // developer build (tools/nonuniform_time.py): slice_shift reports the longest equal-bin run
-    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL>(key, ln, count, scratch, A.dirs == nullptr));
+    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL, TWO_PASS>(key, ln, count, scratch, A.dirs == nullptr));
     else wave_sort<EPT>(key, ln);
 #else
-    if constexpr (BINS) wave_sort_binned<EPT, FULL>(key, ln, count, scratch, A.dirs == nullptr);
+    if constexpr (BINS) wave_sort_binned<EPT, FULL, TWO_PASS>(key, ln, count, scratch, A.dirs == nullptr);
     else wave_sort<EPT>(key, ln);
 #endif
     if (which == 0) {
