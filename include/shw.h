@@ -435,7 +435,8 @@ SHW_API int shw_gsw_circular_backward_dirs(const float* xs, const float* xt, con
  * finite with a positive sum per row; the kernel divides by the sum.  The sign and the sum are NOT checked on the
  * device: a row whose weights sum to 0 or less yields, in bounded time, a value that means nothing.  A zero weight contributes nothing
  * and gets coefficient 0.  With both sides NULL the CDFs are the exact integer grid of lcm(n, m) steps.
- * There is no gradient with respect to the weights.  Cost and coefficients are the same bits on every run.
+ * Gradients with respect to the weights come from the *_pot entries below, not from these.  Cost and coefficients are
+ * the same bits on every run.
  *
  * Rows of keys the caller computed (any defining function).
  *   u (rows, n), v (rows, m) contiguous; rows >= 0, any count.
@@ -476,6 +477,52 @@ SHW_API int shw_line_esw_backward_points(const float* thetas, const float* coef_
 SHW_API int shw_line_esw_backward_dirs(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
                                        const float* slice_w, int pairs, int n, int m, int dim, int slices,
                                        float* grad_thetas, void* stream);
+
+/* Gradients with respect to the weights (the weighted path only; the entries above are unchanged and give none).
+ *
+ * Per row: sorted values u_(0..n-1), v_(0..m-1); normalised masses abar = a / T_a, bbar = b / T_b (T the sum of the raw
+ * weights); CDF ends A_r, B_j, the last end of each side 1.  Walk the merged ends in ascending order; ON EQUAL LEVELS THE
+ * u END COMES FIRST, and segments of zero width count.  Segment k has the active atoms (i_k, j_k) and the cost
+ * c_k = |u_(i_k) - v_(j_k)|^p; it is closed by A_i (then i advances) or by B_j (then j advances); the walk stops at
+ * (n-1, m-1).  The jump at the end that closes segment k is c_k - c_(k+1): phi_r when the end is A_r, psi_j when it is
+ * B_j; the last ends have none.  So phi_r = c(r, j) - c(r+1, j) with j the first v atom with B_j >= A_r, and
+ * psi_j = c(i, j) - c(i, j+1) with i the first u atom with A_i > B_j (the last atom when there is none): one tie rule for
+ * both sides, without which the pair is not a subgradient.
+ *   f_r = sum_{s=r}^{n-2} phi_s, f_(n-1) = 0;   g_j = sum_{s=j}^{m-2} psi_s, g_(m-1) = 0
+ *   d cost / d a_(r) = (f_r - sum_s abar_s f_s) / T_a        d cost / d b_(j) = (g_j - sum_s bbar_s g_s) / T_b
+ * written at the atom's original index.  sum_i a_i * grad_i = 0 on each side (the cost does not change when a side's
+ * weights are scaled), sum abar f + sum bbar g + c_last = cost, and a side with one atom gets exactly 0.  An atom of
+ * weight 0 gets the potential at its position -- the derivative to the right, the rate at which the cost changes when the
+ * atom gains mass -- while its value coefficient stays 0.  The jumps are differences of float32 costs, summed in float32
+ * inside a lane and in double across the 64 lanes and in the mean; the CDF is the 2^30 grid of the entries above.  Cost and
+ * coefficients are the bits of the entries without potentials, and everything is the same bits on every run.
+ *
+ *   pot_u (rows, n) / pot_v (rows, m) out (fused form: (pairs*slices, n) / (pairs*slices, m)), each may be NULL: the
+ *   gradient of that row's (slice's) cost with respect to that row's (pair's) RAW weights.  A row needs its side's weights.
+ *   coef_* may be NULL with pot_* given (gradients with respect to the weights only).
+ * Return hipErrorInvalidValue as the entries without potentials, and on a potential row for a side whose weights are NULL. */
+SHW_API int shw_line_rows_forward_pot(const float* u, const float* v, long rows, int n, int m, float p,
+                                      const float* u_weights, const float* v_weights, long u_weight_stride,
+                                      long v_weight_stride, float* row_cost, float* coef_u, float* coef_v, float* pot_u,
+                                      float* pot_v, void* stream);
+
+SHW_API int shw_line_esw_forward_pot(const float* xs, const float* xt, const float* thetas, int pairs, int n, int m,
+                                     int dim, int slices, long theta_pair_stride, float p, const float* u_weights,
+                                     const float* v_weights, long u_weight_stride, long v_weight_stride,
+                                     float* slice_cost, float* coef_s, float* coef_t, float* pot_u, float* pot_v,
+                                     void* stream);
+
+/* The reduction over slices: grad[b,i] = sum_l slice_w[b,l] * pot[b,l,i], pot (pairs, slices, count), slice_w
+ * (pairs, slices), slices summed in the order l = 0..slices-1; shared == 0: grad (pairs, count).  shared != 0 (one weight
+ * row shared by the pairs): summed over the pairs as well, grad (count): the pairs*slices rows in ascending order, in groups
+ * of 64 rows whose sums are then added in ascending order; this needs `workspace`, device memory of
+ * shw_line_weight_grads_workspace_bytes(pairs, slices, count, shared) bytes (0 bytes: NULL is fine).  The rows form with
+ * shared weights is pairs = 1, slices = rows.  No atomics: the same bits on every run.  1 <= count <= 4096,
+ * 0 <= pairs <= 65535, pairs*slices <= 65535*64 when shared; hipErrorInvalidValue otherwise and on null pointers. */
+SHW_API size_t shw_line_weight_grads_workspace_bytes(int pairs, int slices, int count, int shared);
+
+SHW_API int shw_line_weight_grads(const float* pot, const float* slice_w, int pairs, int slices, int count, int shared,
+                                  void* workspace, float* grad, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Log-domain Sinkhorn distance (comparison metric); value-only entry point.

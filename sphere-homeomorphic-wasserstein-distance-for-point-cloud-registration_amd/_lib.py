@@ -129,6 +129,17 @@ _SIGNATURES = {
                                                     _c_f32p, ctypes.c_void_p]),
     "shw_line_esw_backward_dirs": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_f32p, ctypes.c_void_p]),
+    # ... with the potentials, the gradients w.r.t. the weights: the forward entries' lists plus pot_u, pot_v; the reduction
+    "shw_line_rows_forward_pot": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_float, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, _c_f32p,
+                                                 _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_line_esw_forward_pot": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.c_float, _c_f32p,
+                                                _c_f32p, ctypes.c_long, ctypes.c_long, _c_f32p, _c_f32p, _c_f32p, _c_f32p,
+                                                _c_f32p, ctypes.c_void_p]),
+    "shw_line_weight_grads_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_line_weight_grads": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p, _c_f32p, ctypes.c_void_p]),
     "shw_sinkhorn_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "shw_sinkhorn_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p,
