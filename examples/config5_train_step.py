@@ -14,7 +14,9 @@ The loop is train_W_COS.py:155-175 (`train_one_epoch`): mean-centre both clouds,
   ascent steps with the |norm - 1| regulariser) and the final distance, with the sliced loss `SlicedSphereW` in the
   CSW slot (`--criterion csw`), or the dormant batched wrapper `max_spherical_wassersten_distance_fast`
   (`--criterion ssw_fast`, _fast.py:346-380);
-* phi: a small planar flow (three x + u tanh(w.x + b) layers; the reference's flows come from a vendored package);
+* phi: `--phi planar` (default) a small planar flow (three x + u tanh(w.x + b) layers), `--phi residual` the trainer's own
+  default `shw.Norm_Flow_structure("Residual", n_flow_layer=3)` on the fused kernels (`--phi residual-composed`: the same
+  module forced onto its composed torch path, to price the kernels' share of the step);
 * data: ModelNet-shaped synthetic clouds (no dataset offline): unit-scale random surfaces, random rigid motion
   <= 45 degrees, sigma 0.02 noise (train_W_COS.py:291-295 defaults).
 
@@ -106,12 +108,16 @@ class PlanarFlow(nn.Module):
         return x
 
 
-def build(slices=512, criterion="csw", phi_max_iter=1, seed=0, dev=None, lr=1e-3):
+def build(slices=512, criterion="csw", phi_max_iter=1, seed=0, dev=None, lr=1e-3, phi_kind="planar"):
     dev = dev or torch.device("cuda", 0)
     torch.manual_seed(seed)
     model = IterativePoseRegressor().to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=1.4e-8)
-    phi = PlanarFlow().to(dev)
+    if phi_kind == "planar":
+        phi = PlanarFlow().to(dev)
+    else:                        # train_W_COS.py:390
+        phi = shw.Norm_Flow_structure(flow_name="Residual", n_flow_layer=3).to(dev)
+        phi.fused = phi_kind == "residual"
     phi_op = torch.optim.Adam(phi.parameters(), lr=9.2e-5, weight_decay=1.4e-8)
     if criterion == "csw":      # train_W_COS.py:393,404 with the sliced loss in the CSW slot
         crit = shw.max_cos_disimilarity_wassersten_distance(phi=phi, CSW=shw.SlicedSphereW(dev, p=2, num_projections=slices),
@@ -140,10 +146,10 @@ def train_step(model, opt, crit, template, source, iteration_num=8):
 
 
 def run(batch=32, points=2048, slices=512, steps=10, seed=0, verbose=True, criterion="csw", phi_max_iter=1,
-        iteration_num=8, fresh_batches=False):
+        iteration_num=8, fresh_batches=False, phi_kind="planar"):
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(seed)
-    model, opt, crit = build(slices, criterion, phi_max_iter, seed, dev)
+    model, opt, crit = build(slices, criterion, phi_max_iter, seed, dev, phi_kind=phi_kind)
     template, source = synthetic_batch(batch, points, gen, dev)
     losses, times = [], []
     for it in range(steps):
@@ -187,8 +193,10 @@ if __name__ == "__main__":
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--criterion", default="csw", choices=["csw", "ssw_fast", "plain"])
     ap.add_argument("--phi-max-iter", type=int, default=1)
+    ap.add_argument("--phi", default="planar", choices=["planar", "residual", "residual-composed"])
     a = ap.parse_args()
-    losses, times = run(a.batch, a.points, a.slices, a.steps, criterion=a.criterion, phi_max_iter=a.phi_max_iter)
+    losses, times = run(a.batch, a.points, a.slices, a.steps, criterion=a.criterion, phi_max_iter=a.phi_max_iter,
+                        phi_kind=a.phi)
     med = sorted(times[2:] or times)[len(times[2:] or times) // 2]
     share = ssw_share(a.batch, a.points, a.slices, a.phi_max_iter + 1)
     print(f"median step {1e3 * med:.2f} ms (sliced-loss part {1e3 * share:.2f} ms = {100 * share / med:.0f} %); "

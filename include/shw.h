@@ -697,6 +697,41 @@ SHW_API int shw_emd_units_forward(const float* x, const float* y, int pairs, int
 SHW_API int shw_emd_units_backward(const float* x, const float* y, const void* workspace, const float* w, int pairs, int n,
                                    int m, int kind, float p, float* grad_x, float* grad_y, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The sphere map phi: residual flows on 3-D points (csrc/shw_flow.hip).
+ * Replaces: the values and gradients the trainers take from `Norm_Flow_structure(flow_name="Residual")`
+ * (s2_wasserstein.py:134-163, train_W_COS.py:40,390): `flows` blocks z <- z + MLP(z), the MLP a chain of `layers` pairs
+ * [Swish, Linear] (nets/lipschitz.py:14-67), 3 -> hidden -> ... -> hidden -> 3, the activation BEFORE every linear layer:
+ * a(x) = x sigmoid(gamma x) / 1.1.  The log-determinant the reference estimates and throws away is not computed.
+ * PARAMETERS are packed and EFFECTIVE: per flow, per layer k, in this order
+ *     gamma_k = softplus(beta_k)  (1),   W_eff,k row-major (out_k, in_k),   b_k (out_k)
+ * with W_eff = W / max(1, sigma / coeff) formed by the caller, so shw_flow_residual_param_count(hidden, layers) =
+ * (1 + 4 hidden) + (layers - 2) (1 + hidden^2 + hidden) + (4 + 3 hidden) floats per flow.
+ * ENVELOPE: dim == 3, 1 <= hidden <= 32, 2 <= layers <= 8, 1 <= flows <= 16; anything else is hipErrorInvalidValue.
+ * Finite inputs give finite outputs and gradients (sigmoid of a large negative argument is 0, of a large positive one 1).
+ */
+
+/* 1 inside the envelope, else 0.  Makes no HIP call. */
+SHW_API int shw_flow_residual_supported(int dim, int hidden, int layers, int flows);
+
+/* floats of the packed parameters of ONE flow; 0 outside the envelope */
+SHW_API size_t shw_flow_residual_param_count(int hidden, int layers);
+
+/* bytes of the backward's workspace (partial parameter-gradient vectors, one per workgroup); 0 for points <= 0 */
+SHW_API size_t shw_flow_residual_workspace_bytes(long points, int hidden, int layers, int flows);
+
+/* x (points, 3) fp32, params (flows * param_count) fp32 -> y (points, 3) fp32.  All flows in one launch; points == 0
+ * is a no-op. */
+SHW_API int shw_flow_residual_forward(const float* x, const float* params, long points, int hidden, int layers, int flows,
+                                      float* y, void* stream);
+
+/* gy (points, 3): gradient w.r.t. y.  gx (points, 3) out, gparams (flows * param_count) out, laid out as params; either
+ * may be NULL and is then not computed.  Nothing is saved by the forward: the layer inputs are recomputed from x.
+ * workspace: shw_flow_residual_workspace_bytes bytes, needed only with gparams; it need not be cleared.  gparams is
+ * summed without atomics in a fixed order: the same inputs give the same bits.  points == 0 zeroes gparams. */
+SHW_API int shw_flow_residual_backward(const float* x, const float* params, const float* gy, long points, int hidden,
+                                       int layers, int flows, float* gx, float* gparams, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

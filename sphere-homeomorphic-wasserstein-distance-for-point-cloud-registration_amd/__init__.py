@@ -8,6 +8,8 @@ from .emd import (Cos_disimilarity_W, Geodesic_distance_W, emd_pair_costs, max_p
                   transport_units, wasserstein_distance, wasserstein_distance_geo)
 from .esw import (augmented_sliced_wassersten_distance, augmented_sliced_wasserstein_distance, esw_slice_sums,
                   max_sliced_wasserstein_distance, rand_projections, sliced_wasserstein_distance)
+from .flows import (Norm_Flow_structure, Norm_Flow_structure_optuna, residual_flow, residual_flow_composed,
+                    residual_flow_supported, residual_param_count)
 from .gsw import (GSWD_circular, GSWD_polynomial, cosine_distance_torch, distributional_sliced_wasserstein_distance,
                   gsw_circular_slice_sums, gsw_nn_1, gsw_nn_3, gsw_polynomial_slice_sums, max_GSWD_circular,
                   max_GSWD_polynomial_3, max_GSWD_polynomial_5, max_gsw_nn_1, max_gsw_nn_3, poly_degree, sorted_row_sums)
@@ -30,4 +32,5 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "max_gsw_nn_1", "max_gsw_nn_3", "poly_degree", "sorted_row_sums", "esw_slice_costs", "line_ot_rows",
            "weighted_sliced_wasserstein_distance", "Cos_disimilarity_W", "Geodesic_distance_W", "emd_pair_costs",
            "max_points_emd", "wasserstein_distance", "wasserstein_distance_geo", "transport_pair_costs",
-           "transport_units"]
+           "transport_units", "Norm_Flow_structure", "Norm_Flow_structure_optuna", "residual_flow",
+           "residual_flow_composed", "residual_flow_supported", "residual_param_count"]

@@ -183,6 +183,14 @@ _SIGNATURES = {
     "shw_emd_units_backward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_float, _c_f32p, _c_f32p,
                                               ctypes.c_void_p]),
+    # the sphere map phi (csrc/shw_flow.hip): residual flows on 3-D points from packed effective parameters
+    "shw_flow_residual_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_flow_residual_param_count": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "shw_flow_residual_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_flow_residual_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_int, _c_f32p, ctypes.c_void_p]),
+    "shw_flow_residual_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
