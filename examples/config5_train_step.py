@@ -5,11 +5,12 @@ registration network forward+backward on 1 GPU".
 The loop is train_W_COS.py:155-175 (`train_one_epoch`): mean-centre both clouds, `model(template, source, 8)`,
 `criteria(template, output['transformed_source'], train_or_test="train")`, `loss.backward()`, Adam step.
 
-* network: a PCRNet-SHAPED iterative pose regressor written here from the description of models/pcrnet.py:7-62 and
-  models/mlp_architecture.py (the reference's model is out of scope -- stock nn layers -- but the workload must have
-  its shape): shared point MLP Conv1d 3->64->64->64->128->1024 + ReLU, max-pool over points, 5 FC layers
-  2048->1024->1024->512->512->256 and a 7-d pose head (quaternion + translation), `iteration_num = 8` refinements,
-  each one re-embedding the moved source;
+* network: `--model shaped` (default) a PCRNet-SHAPED iterative pose regressor written here from the description of
+  models/pcrnet.py:7-62 and models/mlp_architecture.py: shared point MLP Conv1d 3->64->64->64->128->1024 + ReLU, max-pool
+  over points, 5 FC layers 2048->1024->1024->512->512->256 and a 7-d pose head (quaternion + translation),
+  `iteration_num = 8` refinements, each one re-embedding the moved source; `--model pcrnet` the package's `shw.PCRNet`
+  (the reference's module and state-dict layout) with the trunk and the max-pool on the fused kernels, `--model
+  pcrnet-composed` the same module forced onto its composed torch path, to price the kernels' share of the step;
 * criterion: the live trainer criterion's shape (s2_wasserstein.py:234-262): phi-max inner loop (`phi_max_iter`
   ascent steps with the |norm - 1| regulariser) and the final distance, with the sliced loss `SlicedSphereW` in the
   CSW slot (`--criterion csw`), or the dormant batched wrapper `max_spherical_wassersten_distance_fast`
@@ -108,10 +109,17 @@ class PlanarFlow(nn.Module):
         return x
 
 
-def build(slices=512, criterion="csw", phi_max_iter=1, seed=0, dev=None, lr=1e-3, phi_kind="planar"):
+def build(slices=512, criterion="csw", phi_max_iter=1, seed=0, dev=None, lr=1e-3, phi_kind="planar", model="shaped"):
     dev = dev or torch.device("cuda", 0)
     torch.manual_seed(seed)
-    model = IterativePoseRegressor().to(dev)
+    if model == "shaped":
+        model = IterativePoseRegressor().to(dev)
+    elif model in ("pcrnet", "pcrnet-composed"):
+        fused = model == "pcrnet"
+        model = shw.PCRNet().to(dev)
+        model.feature_model.fused = fused
+    else:
+        raise ValueError(model)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=1.4e-8)
     if phi_kind == "planar":
         phi = PlanarFlow().to(dev)
@@ -146,10 +154,10 @@ def train_step(model, opt, crit, template, source, iteration_num=8):
 
 
 def run(batch=32, points=2048, slices=512, steps=10, seed=0, verbose=True, criterion="csw", phi_max_iter=1,
-        iteration_num=8, fresh_batches=False, phi_kind="planar"):
+        iteration_num=8, fresh_batches=False, phi_kind="planar", model="shaped"):
     dev = torch.device("cuda", 0)
     gen = torch.Generator().manual_seed(seed)
-    model, opt, crit = build(slices, criterion, phi_max_iter, seed, dev, phi_kind=phi_kind)
+    model, opt, crit = build(slices, criterion, phi_max_iter, seed, dev, phi_kind=phi_kind, model=model)
     template, source = synthetic_batch(batch, points, gen, dev)
     losses, times = [], []
     for it in range(steps):
@@ -194,9 +202,10 @@ if __name__ == "__main__":
     ap.add_argument("--criterion", default="csw", choices=["csw", "ssw_fast", "plain"])
     ap.add_argument("--phi-max-iter", type=int, default=1)
     ap.add_argument("--phi", default="planar", choices=["planar", "residual", "residual-composed"])
+    ap.add_argument("--model", default="shaped", choices=["shaped", "pcrnet", "pcrnet-composed"])
     a = ap.parse_args()
     losses, times = run(a.batch, a.points, a.slices, a.steps, criterion=a.criterion, phi_max_iter=a.phi_max_iter,
-                        phi_kind=a.phi)
+                        phi_kind=a.phi, model=a.model)
     med = sorted(times[2:] or times)[len(times[2:] or times) // 2]
     share = ssw_share(a.batch, a.points, a.slices, a.phi_max_iter + 1)
     print(f"median step {1e3 * med:.2f} ms (sliced-loss part {1e3 * share:.2f} ms = {100 * share / med:.0f} %); "

@@ -732,6 +732,43 @@ SHW_API int shw_flow_residual_forward(const float* x, const float* params, long 
 SHW_API int shw_flow_residual_backward(const float* x, const float* params, const float* gy, long points, int hidden,
                                        int layers, int flows, float* gx, float* gparams, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The registration network's trunk: PointNet point MLP fused with the max-pool (csrc/shw_pointnet.hip).
+ * Replaces: `Pooling()(MLP_Architecture(emb)(x))` of models/pcrnet.py:29,49 -- five 1x1 convolutions 3 -> 64 -> 64 -> 64
+ * -> 128 -> emb, a ReLU after each, and the maximum over the points.  max_i relu(z_i) = relu(max_i z_i), so the last
+ * layer's (clouds, emb, points) output is never stored: the forward keeps a running maximum and its arg-max, and the
+ * backward recomputes the hidden layers on the arg-max points only, one row per (cloud, channel).
+ * PARAMETERS are packed: W1 (64, 3) b1 (64) W2 (64, 64) b2 W3 (64, 64) b3 W4 (128, 64) b4 W5 (emb, 128) b5 (emb), each
+ * weight row-major (out, in) = Conv1d's (out, in, 1); 16-byte aligned.
+ * ENVELOPE: dim == 3, emb % 32 == 0, 32 <= emb <= 2048, clouds >= 1, 1 <= points < 2^31; anything else is
+ * hipErrorInvalidValue.  Layers 2..5 run on the exact-f32 matrix instruction: every dot product is an f32 fmaf chain.
+ * Neither entry allocates, synchronises or reads back; both can be captured into a graph.
+ */
+
+/* 1 inside the envelope, else 0.  Makes no HIP call. */
+SHW_API int shw_pointnet_supported(int dim, int emb);
+
+/* floats of the packed parameters, 16 896 + 129 emb; 0 outside the envelope */
+SHW_API size_t shw_pointnet_param_count(int emb);
+
+/* bytes of the workspace of the forward (backward == 0: per-tile maxima, clouds * ceil(points / 64) * emb pairs) or of the
+ * backward (per-row point gradients and per-workgroup partial parameter gradients); 0 outside the envelope */
+SHW_API size_t shw_pointnet_workspace_bytes(long clouds, long points, int emb, int backward);
+
+/* x (clouds, points, 3) fp32 -> feat (clouds, emb) = relu(max over the points of the last pre-activation) and argmax
+ * (clouds, emb) int32, the point index of that maximum.  Ties go to the lowest index; argmax is in [0, points) whatever
+ * the input holds, also for channels whose feature is 0.  workspace need not be cleared. */
+SHW_API int shw_pointnet_forward(const float* x, const float* params, long clouds, long points, int emb, float* feat,
+                                 int* argmax, void* workspace, void* stream);
+
+/* gfeat (clouds, emb): gradient w.r.t. feat; feat and argmax as the forward returned them.  gx (clouds, points, 3) out:
+ * zero except at arg-max points, the channels of one point added in ascending channel order.  gparams out, laid out as
+ * params.  Either may be NULL and is then not computed.  A channel with feat == 0 passes nothing.  Sums run in a fixed
+ * order without atomics: the same inputs give the same bits.  workspace (16-byte aligned) need not be cleared. */
+SHW_API int shw_pointnet_backward(const float* x, const float* params, const float* feat, const int* argmax,
+                                  const float* gfeat, long clouds, long points, int emb, float* gx, float* gparams,
+                                  void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ from .gsw import (GSWD_circular, GSWD_polynomial, cosine_distance_torch, distrib
 from .line_ot import esw_slice_costs, line_ot_rows, weighted_sliced_wasserstein_distance
 from .modules import (ChamferCriterion, GraphedAscent, GraphedStep, SlicedSphereW, SSWCriterion, max_cos_disimilarity_wassersten_distance,
                       max_spherical_wassersten_distance, max_spherical_wassersten_distance_fast)
+from .pcrnet import (MLP_Architecture, PCRNet, Pooling, convert2transformation, create_pose_7d, get_quaternion,
+                     get_translation, pointnet_max_features, pointnet_max_features_composed, pointnet_param_count,
+                     pointnet_supported, qrot, quaternion_rotate, quaternion_transform, unpack_pointnet_params)
 from .sinkhorn import (log_N_Sinkhorn_Distance_Loss, log_Sinkhorn_Distance_Loss, sinkhorn_barycentric_map,
                        sinkhorn_pair_costs)
 from .ssw import (binary_search_circle, circle_coordinates, draw_directions, emd1D_circle, enable_float64, enable_float64_general, float64_enabled,
@@ -33,4 +36,7 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "weighted_sliced_wasserstein_distance", "Cos_disimilarity_W", "Geodesic_distance_W", "emd_pair_costs",
            "max_points_emd", "wasserstein_distance", "wasserstein_distance_geo", "transport_pair_costs",
            "transport_units", "Norm_Flow_structure", "Norm_Flow_structure_optuna", "residual_flow",
-           "residual_flow_composed", "residual_flow_supported", "residual_param_count"]
+           "residual_flow_composed", "residual_flow_supported", "residual_param_count", "MLP_Architecture", "PCRNet",
+           "Pooling", "convert2transformation", "create_pose_7d", "get_quaternion", "get_translation",
+           "pointnet_max_features", "pointnet_max_features_composed", "pointnet_param_count", "pointnet_supported", "qrot",
+           "quaternion_rotate", "quaternion_transform", "unpack_pointnet_params"]

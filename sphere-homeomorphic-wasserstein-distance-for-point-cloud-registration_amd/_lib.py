@@ -191,6 +191,15 @@ _SIGNATURES = {
                                                  ctypes.c_int, _c_f32p, ctypes.c_void_p]),
     "shw_flow_residual_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_int, ctypes.c_int,
                                                   ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    # the registration network's trunk (csrc/shw_pointnet.hip): PointNet point MLP fused with the max-pool
+    "shw_pointnet_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "shw_pointnet_param_count": (ctypes.c_size_t, [ctypes.c_int]),
+    "shw_pointnet_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int]),
+    "shw_pointnet_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_int, _c_f32p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "shw_pointnet_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_long,
+                                             ctypes.c_long, ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p,
+                                             ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
