@@ -156,6 +156,47 @@ SHW_API int shw_circle_ot(const float* u, const float* v, const float* wu, const
                           float* grad_u, float* grad_v, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Gradients with respect to the WEIGHTS of weighted clouds on the circle (additive to ABI 3; csrc/shw_ssw_weights.hip).
+ * The reference cannot serve as the statement here: binary_search_circle ends in Cost(tc.detach(), ...) (:207), so its
+ * autograd differentiates Cost at a fixed cut, while with weights the minimising cut sits on a kink of cut -> Cost -- a
+ * source level A_r = a_(1) + .. + a_(r) meeting a rotated target level B_j - cut -- that moves with the weights.  These
+ * entries return the gradient of W(a, b) = min over the cut of Cost(cut; a, b), weights in sorted order, A / B the CDFs:
+ *   fixed cut : ga_i = sum_(r >= i, r < n-1) [c(u_r, y) - c(u_(r+1), y)],  y the rotated target atom active at level A_r,
+ *               gb_k = sum_(j >= k) [c(x, v_j) - c(x, v_next(j))], x the source atom active at level B_j - cut and next(j)
+ *               the next target atom around the circle (one turn later after the last); the sum runs over the target's
+ *               own sorted order, whatever the cut wraps.  d Cost / d cut = -(sum of all target jumps).
+ *   W         : G = lambda G+ + (1 - lambda) G-, the fixed-cut gradients on the two sides of the kink (ties resolved
+ *               target level first / source level first), lambda = -s- / (s+ - s-) with s+- the two slopes in the cut,
+ *               clipped to [0, 1], 0.5 when both are 0.  Equivalently d W / d a_i = ga_i - s [i <= r],
+ *               d W / d b_k = gb_k + s [k <= j] on either side, for the kink cut* = B_j - A_r.  With exactly tied levels
+ *               (W has no gradient) the mix is a subgradient of the convex W.
+ *   p == 1 level median (emd1D_circle's formula, its quirk included): in merged order, gaps g_k, signed weights +a / -b,
+ *               level_k their running sum, median level_(k*), sigma_k = sign(level_k - median), H_k = sum_(t >= k) g_t
+ *               sigma_t, S = H_0: the derivative w.r.t. the signed weight at k is H_k - S [k <= k*] (negated for a target atom).
+ * The two sides are evaluated at t - 3e-7 and t + 3e-7 (levels compared in double), t the cut: the fp32 cut of the solve
+ * is within rounding of the kink at best.  Where both slopes there have one sign (the solve also ends once nothing is left
+ * to gain in the COST, possibly many kinks from the minimiser) t is moved until the window holds the minimum, and a window
+ * that holds several kinks is narrowed, down to 1e-9: at most 48 evaluations per row, one when the solve ended on the kink.
+ * Jumps are differences of fp32 costs summed in double in a fixed order (the same bits on every run).  Weights are taken
+ * as normalised (sum 1, >= 0), so each row is returned centred, (G_i - sum_s a_s G_s / T) / T with T = sum a: the gradient
+ * of the cost composed with w -> w / sum w; sum_i a_i G_i = 0.  A side of one atom gets exactly 0; an atom of weight 0 gets
+ * the potential at its position.  The solve is not repeated: the cut is an INPUT, the one shw_ssw_forward_general
+ * (slice_theta) / shw_circle_ot (aux) wrote for the same clouds and weights.
+ *   slice_cut / cut (pairs*slices) / (rows) in; may be NULL where p == 1 takes the level median;
+ *   pot_u (pairs*slices, n) / (rows, n), pot_v (pairs*slices, m) / (rows, m) out, by original index; one may be NULL.
+ *   A potential row needs its side's weights (the other side's may be NULL = uniform).  1 <= n, m <= 4096.
+ * The reduction over slices, grad[b,i] = sum_l w[b,l] pot[b,l,i], is shw_line_weight_grads below.
+ * shw_circle_weight_potentials takes shw_circle_ot's `method`.  Return hipErrorInvalidValue on anything else. */
+SHW_API int shw_ssw_weight_potentials(const float* xs, const float* xt, const float* dirs, const float* wu, const float* wv,
+                                      long wu_pair_stride, long wv_pair_stride, int pairs, int n, int m, int slices,
+                                      long u_pair_stride, float p, const float* slice_cut, float* pot_u, float* pot_v,
+                                      void* stream);
+
+SHW_API int shw_circle_weight_potentials(const float* u, const float* v, const float* wu, const float* wv,
+                                         long wu_row_stride, long wv_row_stride, int rows, int n, int m, float p, int method,
+                                         const float* cut, float* pot_u, float* pot_v, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Float64 path: equal cloud sizes, uniform weights, any p >= 1 (additive to ABI 3).
  * The reference takes its arithmetic type from its input (`dtype = u_values.dtype`, max_spherical_sliced_w.py:153-160;
  * _fast.py:157, :221): double clouds and double directions give a double loss and double gradients.  These entries are

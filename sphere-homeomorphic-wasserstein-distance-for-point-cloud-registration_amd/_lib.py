@@ -39,6 +39,13 @@ _SIGNATURES = {
     "shw_circle_ot": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, _c_f32p, _c_f32p, _c_f32p,
                                      _c_f32p, ctypes.c_void_p]),
+    # gradients w.r.t. the weights on the circle (csrc/shw_ssw_weights.hip): potential rows at the cut the solve left
+    "shw_ssw_weight_potentials": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long,
+                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long,
+                                                 ctypes.c_float, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_circle_weight_potentials": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                                    _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p]),
     # float64 path (csrc/shw_ssw_f64.hip): equal sizes, uniform weights
     "shw_max_points_f64": (ctypes.c_int, []),
     "shw_stiefel_frames_f64": (ctypes.c_int, [_c_f32p, ctypes.c_long, _c_f32p, ctypes.c_void_p]),

@@ -22,7 +22,12 @@ Weighted and unequal-size double clouds are a SECOND opt-in on top of it, `enabl
 SHW_FLOAT64_GENERAL=1): kernels of csrc/shw_ssw_f64_general.hip, up to `max_points_f64_general()` points per cloud, the
 exact minimum over the cut for p != 1 and the level-median formula for p == 1.  While it is off such calls raise the
 ValueError they always raised, so that a loader that drops one point does not silently move a caller from the
-equal-size kernel to a much slower one.  Weights have the clouds' dtype and are not differentiable.
+equal-size kernel to a much slower one.  Weights have the clouds' dtype.
+Float32 weights that require grad (under an enabled grad mode) stay in the graph and receive a gradient of their own shape
+on every path that takes weights: the sliced functions in R^3 and on S^(d-1), `binary_search_circle`, `emd1D_circle`
+(kernels of csrc/shw_ssw_weights.hip).  It is the gradient of the minimum over the cut -- not the
+reference's autograd, which stops at its detached cut -- resp. the derivative of the level-median formula; weights count
+as normalised and the gradient is centred, sum_i w_i grad_i = 0.  Float64 weights are detached, as before.
 """
 from __future__ import annotations
 
@@ -348,10 +353,12 @@ class _PairLosses(torch.autograd.Function):
             cost2d = ws.slice_cost.view(B, L).clone()
             shift2d = torch.zeros(B, L, dtype=torch.int32, device=dev) if general else ws.slice_aux.view(B, L).clone()
             ctx.mark_non_differentiable(cost2d, shift2d)
-        if need_grad:
+        need_w = (not f64) and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6])   # (weights in the graph: _check_weights)
+        if need_grad or need_w:
             ctx.save_for_backward(Xs_c, Xt_c, Us_c)
-            ctx.lease = _Lease(ws)                  # the coefficients stay put until this node dies
+            ctx.lease = _Lease(ws)                  # the coefficients (and the cuts) stay put until this node dies
             ctx.dims = (B, n, m, L, stride)
+            ctx.weights = (wu, wv, float(p)) if need_w else None
             ctx.set_materialize_grads(False)
         else:
             ws.release()                            # stream-ordered: the next lease is on the same stream
@@ -368,6 +375,27 @@ class _PairLosses(torch.autograd.Function):
         dev = Xs_c.device
         if g_pair is None and g_total is None and g_first is None:
             return (None,) * 9
+        gwu = gwv = None
+        if ctx.weights is not None and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):
+            # potential rows of every slice at the cut the solve left in the workspace, then the reduction over slices
+            wu, wv, p = ctx.weights
+            want_u, want_v = ctx.needs_input_grad[5], ctx.needs_input_grad[6]
+            pu = torch.empty(B * L, n, dtype=torch.float32, device=dev) if want_u else None
+            pv = torch.empty(B * L, m, dtype=torch.float32, device=dev) if want_v else None
+            wud, wvd = (wu.detach() if wu is not None else None), (wv.detach() if wv is not None else None)
+            rows_w = _upstream_rows(g_pair, g_total, g_first, B, torch.float32, dev)
+            slice_w = (rows_w / L).unsqueeze(1).expand(B, L).contiguous()
+            with torch.cuda.device(dev):
+                _lib.check(lib.shw_ssw_weight_potentials(
+                    Xs_c.data_ptr(), Xt_c.data_ptr(), Us_c.data_ptr(), wud.data_ptr() if wud is not None else None,
+                    wvd.data_ptr() if wvd is not None else None, 0 if wud is None or wud.dim() == 1 else n,
+                    0 if wvd is None or wvd.dim() == 1 else m, B, n, m, L, stride, p, ws.slice_aux.data_ptr(),
+                    pu.data_ptr() if want_u else None, pv.data_ptr() if want_v else None, _stream_ptr(dev)),
+                    "shw_ssw_weight_potentials")
+            if want_u:
+                gwu = _reduce_potentials(pu, slice_w, B, L, n, wu.dim() == 1)
+            if want_v:
+                gwv = _reduce_potentials(pv, slice_w, B, L, m, wv.dim() == 1)
         want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         want_dirs = ctx.needs_input_grad[2]
         # the upstream gradients go to the kernel as they are: row b is scaled by g_pair[b] + g_total[0] there
@@ -403,7 +431,7 @@ class _PairLosses(torch.autograd.Function):
                                               1.0 / L, gp_ptr, gt_ptr, gU.data_ptr(), _stream_ptr(dev)), name)
                 if stride == 0:
                     gU = gU.sum(0)
-        return gxs, gxt, gU, None, None, None, None, None, None
+        return gxs, gxt, gU, None, None, gwu, gwv, None, None
 
 
 class _PairLossesDim(torch.autograd.Function):
@@ -446,10 +474,13 @@ class _PairLossesDim(torch.autograd.Function):
             cost2d = ws.slice_cost.view(B, L).clone()
             shift2d = torch.zeros(B, L, dtype=torch.int32, device=dev) if general else ws.slice_aux.view(B, L).clone()
             ctx.mark_non_differentiable(cost2d, shift2d)
-        if need_grad:
+        need_w = ctx.needs_input_grad[5] or ctx.needs_input_grad[6]
+        if need_grad or need_w:
             ctx.save_for_backward(Xs_c, Xt_c, Us_c)
-            ctx.lease = _Lease(ws)                  # the coefficients stay put until this node dies
+            ctx.lease = _Lease(ws)                  # the coefficients (and the cuts) stay put until this node dies
             ctx.dims = (B, n, m, d, L, stride)
+            # weight gradients run the circle-level kernel on the coordinate rows written above: they stay with the node
+            ctx.weights = (wu, wv, float(p), coords) if need_w else None
             ctx.set_materialize_grads(False)
         else:
             ws.release()
@@ -464,6 +495,32 @@ class _PairLossesDim(torch.autograd.Function):
         dev = Xs_c.device
         if g_pair is None and g_total is None and g_first is None:
             return (None,) * 9
+        gwu = gwv = None
+        if ctx.weights is not None and (ctx.needs_input_grad[5] or ctx.needs_input_grad[6]):
+            wu, wv, p, coords = ctx.weights
+            want_u, want_v = ctx.needs_input_grad[5], ctx.needs_input_grad[6]
+            pu = torch.empty(B * L, n, dtype=torch.float32, device=dev) if want_u else None
+            pv = torch.empty(B * L, m, dtype=torch.float32, device=dev) if want_v else None
+            wud, wvd = (wu.detach() if wu is not None else None), (wv.detach() if wv is not None else None)
+            rows_w = _upstream_rows(g_pair, g_total, g_first, B, torch.float32, dev)
+            slice_w = (rows_w / L).unsqueeze(1).expand(B, L).contiguous()
+            per_pair = (wud is not None and wud.dim() == 2) or (wvd is not None and wvd.dim() == 2)
+            # (per-pair weights: one launch per pair, as the forward -- a row stride cannot say "one weight row per L rows")
+            groups = [(b * L, L, b) for b in range(B)] if per_pair else [(0, B * L, 0)]
+            cu, cv = coords.data_ptr(), coords.data_ptr() + 4 * B * L * n
+            with torch.cuda.device(dev):
+                for r0, cnt, b in groups:
+                    _lib.check(lib.shw_circle_weight_potentials(
+                        cu + 4 * r0 * n, cv + 4 * r0 * m,
+                        None if wud is None else wud.data_ptr() + (4 * b * n if wud.dim() == 2 else 0),
+                        None if wvd is None else wvd.data_ptr() + (4 * b * m if wvd.dim() == 2 else 0), 0, 0, cnt, n, m, p,
+                        _lib.CIRCLE_AS_SLICED, ws.slice_aux.data_ptr() + 4 * r0,
+                        pu.data_ptr() + 4 * r0 * n if want_u else None, pv.data_ptr() + 4 * r0 * m if want_v else None,
+                        _stream_ptr(dev)), "shw_circle_weight_potentials")
+            if want_u:
+                gwu = _reduce_potentials(pu, slice_w, B, L, n, wu.dim() == 1)
+            if want_v:
+                gwv = _reduce_potentials(pv, slice_w, B, L, m, wv.dim() == 1)
         want_points = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         want_dirs = ctx.needs_input_grad[2]
         gp = g_pair.to(torch.float32).contiguous() if g_pair is not None else None
@@ -493,7 +550,7 @@ class _PairLossesDim(torch.autograd.Function):
                     "shw_ssw_backward_dirs_dim")
                 if stride == 0:
                     gU = gU.sum(0)
-        return gxs, gxt, gU, None, None, None, None, None, None
+        return gxs, gxt, gU, None, None, gwu, gwv, None, None
 
 
 def _check_weights(name, w, count, B, dev, dtype=torch.float32):
@@ -506,7 +563,38 @@ def _check_weights(name, w, count, B, dev, dtype=torch.float32):
         raise TypeError(f"{name} must be a float32 device tensor")
     if tuple(w.shape) not in ((count,), (B, count)):
         raise ValueError(f"{name} must have shape ({count},) or ({B}, {count}), got {tuple(w.shape)}")
+    if dtype == torch.float32 and w.requires_grad and torch.is_grad_enabled():
+        return w.contiguous()                   # stays in the graph: the weight-gradient kernels (float32 only)
     return w.detach().contiguous()
+
+
+def _reduce_potentials(pot, slice_w, pairs, slices, count, shared):
+    """grad[b,i] = sum_l slice_w[b,l] pot[b,l,i] (`shw_line_weight_grads`: fixed order, no atomics): (pairs, count), or
+    (count,) summed over the pairs as well for a weight row they share."""
+    lib = _lib.load()
+    dev = pot.device
+    if pairs > 65535 or (shared and pairs * slices > 65535 * 64):
+        raise ValueError("weight gradients: more than 65535 pairs, or weights shared by more than 65535 * 64 slices: "
+                         "split the call")
+    grad = torch.empty((count,) if shared else (pairs, count), dtype=torch.float32, device=dev)
+    nbytes = lib.shw_line_weight_grads_workspace_bytes(pairs, slices, count, int(shared))
+    work = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.shw_line_weight_grads(pot.data_ptr(), slice_w.data_ptr(), pairs, slices, count, int(shared),
+                                             work.data_ptr() if work is not None else None, grad.data_ptr(),
+                                             _stream_ptr(dev)), "shw_line_weight_grads")
+    return grad
+
+
+def _upstream_rows(g_pair, g_total, g_first, B, dtype, dev):
+    """The upstream gradients of the three loss outputs as one (B,) row weight, or None when there is none."""
+    gp = g_pair.to(dtype).contiguous() if g_pair is not None else None
+    if g_first is not None:                     # gradient of the 0-dim first-pair output: belongs to row 0
+        gp = gp.clone() if gp is not None else torch.zeros(B, dtype=dtype, device=dev)
+        gp[0] += g_first.to(dtype)
+    if g_total is not None:
+        gp = gp + g_total.to(dtype).reshape(1) if gp is not None else g_total.to(dtype).reshape(1).expand(B)
+    return gp
 
 
 def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weights=None, return_total=False,
@@ -526,7 +614,12 @@ def ssw_pair_losses(Xs, Xt, Us, p=2, return_slices=False, u_weights=None, v_weig
     not change when a frame is rotated in its plane or scaled, <g[:,0], u2> = <g[:,1], u1> and <g[:,0], u1> = -<g[:,1], u2>.
     Backward launches the point-gradient kernel only if a cloud requires grad and the frame-gradient kernel
     (csrc/shw_ssw_dirs.hip) only if `Us` does; with frames that do not require grad nothing differs from before, and
-    with frames that do, the loss and the point gradients keep their bits.  Weights are not differentiable."""
+    with frames that do, the loss and the point gradients keep their bits.
+    Float32 weights that require grad receive `.grad` of their own shape ((n,) shared: summed over the pairs): backward then
+    launches the potential kernel (csrc/shw_ssw_weights.hip) for the sides that need it and `shw_line_weight_grads` for the
+    reduction over slices; with or without gradients to the clouds and the frames, whose bits, like the loss's, do not
+    change.  With no weight requiring grad nothing is launched or allocated that was not before.  Float64 weights are
+    detached: not differentiable."""
     _check_sphere_cloud("Xs", Xs)
     _check_sphere_cloud("Xt", Xt)
     _check_cloud_dirs(Us)
@@ -649,7 +742,8 @@ def max_sliced_wasserstein_sphere(Xs, Xt, num_projections=1, device=None, p=2, m
     """Max-sliced spherical W: the frames are drawn as `sliced_wasserstein_sphere` / `_fast` draw them
     (`draw_directions`, the global torch generator), moved by `max_iter` Adam ASCENT steps (step size `lr`) on the loss
     against the detached clouds -- the frame gradient of `ssw_pair_losses` -- and brought back to the Stiefel manifold
-    after every step by `retract_frames`; then the loss at the final frames, differentiable in the clouds.
+    after every step by `retract_frames`; then the loss at the final frames, differentiable in the clouds (and in float32
+    weights that require grad: they are detached during the ascent).
     Xs (n,d), Xt (m,d) -> 0-dim tensor; Xs (B,n,d), Xt (B,m,d) -> shape-[1] tensor (per-pair frames), as `sliced_cost`.
     `device` None: the clouds' device.  With `return_frames` also the final frames, (L,d,2) resp. (B,L,d,2), detached.
     The counterpart of `max_sliced_wasserstein_distance` (Euclidean) and `max_GSWD_*` (generalised) for the sphere."""
@@ -657,10 +751,13 @@ def max_sliced_wasserstein_sphere(Xs, Xt, num_projections=1, device=None, p=2, m
     batch = Xs.shape[0] if Xs.dim() == 3 else None
     U = draw_directions(num_projections, device, batch=batch, d=Xs.shape[-1], dtype=Xs.dtype).requires_grad_(True)
     xs_d, xt_d = Xs.detach(), Xt.detach()
+    # (the ascent is on the frames alone: weights that require grad take part in the final evaluation only)
+    uw_d = u_weights.detach() if isinstance(u_weights, torch.Tensor) else u_weights
+    vw_d = v_weights.detach() if isinstance(v_weights, torch.Tensor) else v_weights
     optimizer = torch.optim.Adam([U], lr=lr)
     with torch.enable_grad():
         for _ in range(max_iter):
-            value = sliced_cost(xs_d, xt_d, U, p=p, u_weights=u_weights, v_weights=v_weights)
+            value = sliced_cost(xs_d, xt_d, U, p=p, u_weights=uw_d, v_weights=vw_d)
             optimizer.zero_grad()
             (-value.sum()).backward()
             optimizer.step()
@@ -712,19 +809,51 @@ class _CircleOT(torch.autograd.Function):
             if need_grad:
                 ctx.save_for_backward(gu, gv)
             return cost
+        need_w = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        cut = torch.empty(rows, dtype=torch.float32, device=dev) if need_w else None   # the cut the bisection ends on
         with torch.cuda.device(dev):
             _lib.check(lib.shw_circle_ot(uc.data_ptr(), vc.data_ptr(), wu_p, wv_p, wu_s, wv_s, rows, n, m, float(p),
-                                         int(method), cost.data_ptr(), None, gu.data_ptr() if need_grad else None,
-                                         gv.data_ptr() if need_grad else None, _stream_ptr(dev)), "shw_circle_ot")
+                                         int(method), cost.data_ptr(), cut.data_ptr() if need_w else None,
+                                         gu.data_ptr() if need_grad else None, gv.data_ptr() if need_grad else None,
+                                         _stream_ptr(dev)), "shw_circle_ot")
         if need_grad:
             ctx.save_for_backward(gu, gv)
+        if need_w:
+            ctx.weights = (uc, vc, wu, wv, float(p), int(method), cut)
         return cost
 
     @staticmethod
     def backward(ctx, g):
-        gu, gv = ctx.saved_tensors
-        w = g.to(gu.dtype).unsqueeze(1)
-        return gu * w, gv * w, None, None, None, None, None
+        gu = gv = gwu = gwv = None
+        if ctx.saved_tensors:
+            gu, gv = ctx.saved_tensors
+            w = g.to(gu.dtype).unsqueeze(1)
+            gu, gv = gu * w, gv * w
+        weights = getattr(ctx, "weights", None)
+        if weights is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4]):
+            # potential rows at the cut the forward kept; a weight row shared by the rows: the reduction over the rows
+            lib = _lib.load()
+            uc, vc, wu, wv, p, method, cut = weights
+            rows, n = uc.shape
+            m = vc.shape[1]
+            dev = uc.device
+            want_u, want_v = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+            pu = torch.empty(rows, n, dtype=torch.float32, device=dev) if want_u else None
+            pv = torch.empty(rows, m, dtype=torch.float32, device=dev) if want_v else None
+            wud, wvd = (wu.detach() if wu is not None else None), (wv.detach() if wv is not None else None)
+            with torch.cuda.device(dev):
+                _lib.check(lib.shw_circle_weight_potentials(
+                    uc.data_ptr(), vc.data_ptr(), wud.data_ptr() if wud is not None else None,
+                    wvd.data_ptr() if wvd is not None else None, 0 if wud is None or wud.dim() == 1 else n,
+                    0 if wvd is None or wvd.dim() == 1 else m, rows, n, m, p, method, cut.data_ptr(),
+                    pu.data_ptr() if want_u else None, pv.data_ptr() if want_v else None, _stream_ptr(dev)),
+                    "shw_circle_weight_potentials")
+            g32 = g.to(torch.float32).contiguous()
+            if want_u:
+                gwu = _reduce_potentials(pu, g32, 1, rows, n, True) if wu.dim() == 1 else pu * g32.unsqueeze(1)
+            if want_v:
+                gwv = _reduce_potentials(pv, g32, 1, rows, m, True) if wv.dim() == 1 else pv * g32.unsqueeze(1)
+        return gu, gv, None, gwu, gwv, None, None
 
 
 def _check_rows(name, t):
