@@ -52,6 +52,13 @@
 //
 // LDS per wave: NB counters (128*EPT bytes) + a 64*EPT-float staging buffer (256*EPT bytes).  LDS operations of one
 // wave execute in order and nothing here is shared with another wave: no barrier.
+// The headline loss kernel (2048 points, one wave, p = 2) asks for the same block and lays it out otherwise (round 28;
+// wave_sort_binned, ALIAS_BPL): 1280 counters, 5120 bytes, start where the 1024 did and run on UNDER the first 1024 bytes of
+// the staging buffer, which has not moved (bytes 4096 .. 12 287).  A counter and a staged key are never alive together:
+// the placement takes all 32 positions of a lane before it writes the first key (binsort_place_full_two_step), and the
+// next sort zeroes the counters behind this one's read-back.  More bins, shorter runs: g ~ 7.6 instead of 8.4 phases; the
+// counters are scanned 20 per lane -- a lane stride of 80 bytes, on which the scan's ds_read_b128 meet no bank conflict
+// (at 128 bytes, 2048 bins, they do, and the kernel is 27 % slower: profiles/r28_forward_summary.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -156,6 +163,35 @@ __device__ __forceinline__ int binsort_scan(unsigned* cnt, int lane) {
   for (int j = 0; j < BPL / 4; ++j)
     *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) =
         u32x4{c[4 * j] + base, c[4 * j + 1] + base, c[4 * j + 2] + base, c[4 * j + 3] + base};
+  __builtin_amdgcn_wave_barrier();
+  return __builtin_amdgcn_readlane(wave_inclusive_max_dpp((int)run), 63);
+}
+
+// The same scan for the counters that lie under the staging buffer (the headline loss kernel: 20 per lane), the lane's
+// sum first: sum and largest counter two counters at a time (v_add3_u32, v_max3_u32), the wave scan of the sums gives the
+// lane's base, and the running sum that is written back STARTS at the base -- one add per counter where binsort_scan pays
+// the in-lane prefix and then the base (per counter: an add and half a v_add3 / v_max3 against two adds and a v_max).
+// `total` = the sum over all counters (wave-uniform).
+template <int BPL>
+__device__ __forceinline__ int binsort_scan_sum_first(unsigned* cnt, int lane, unsigned& total) {
+  unsigned c[BPL];
+  unsigned run = 0, sum = 0;
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(cnt + lane * BPL + j * 4);
+    c[4 * j] = v.x; c[4 * j + 1] = v.y; c[4 * j + 2] = v.z; c[4 * j + 3] = v.w;
+    sum += v.x + v.y; sum += v.z + v.w;
+    run = max(max(v.x, v.y), run); run = max(max(v.z, v.w), run);
+  }
+  const int incl = wave_inclusive_scan_dpp((int)sum);
+  total = (unsigned)__builtin_amdgcn_readlane(incl, 63);
+  unsigned at = (unsigned)incl - sum;
+#pragma unroll
+  for (int j = 0; j < BPL / 4; ++j) {
+    u32x4 w;
+    w.x = at; at += c[4 * j]; w.y = at; at += c[4 * j + 1]; w.z = at; at += c[4 * j + 2]; w.w = at; at += c[4 * j + 3];
+    *reinterpret_cast<u32x4*>(cnt + lane * BPL + j * 4) = w;
+  }
   __builtin_amdgcn_wave_barrier();
   return __builtin_amdgcn_readlane(wave_inclusive_max_dpp((int)run), 63);
 }
@@ -381,11 +417,12 @@ __device__ __forceinline__ void binsort_read_back_and_fix(float (&key)[EPT], int
 // first sorted position of every bin, in bytes).  key[r] belongs to point r*64 + lane.  No rank is returned:
 // binsort_place_full takes the position from an atomic on the scanned starts.  slot[r] = LDS address of the counter of
 // key[r], kept for binsort_place_full.
-template <int EPT>
+// NB: the bin count -- binsort_bins<EPT>() everywhere but in the headline loss kernel, whose counters lie under the staging
+// buffer and may be more (wave_sort_binned, ALIAS_BPL).
+template <int EPT, int NB = binsort_bins<EPT>()>
 __device__ __forceinline__ int binsort_histogram_full(const float (&key)[EPT], int lane, unsigned* cnt, unsigned (&slot)[EPT]) {
-  constexpr int NB = binsort_bins<EPT>();
   constexpr int BPL = NB / 64;                          // bins per lane in the scan (EPT/2: 16 at EPT = 32)
-  static_assert(BPL >= 4 && BPL % 4 == 0, "bin sort needs >= 4 bins per lane");
+  static_assert(BPL >= 4 && BPL % 4 == 0 && NB == 64 * BPL, "bin sort needs >= 4 bins per lane, a multiple of four");
   // zero the counters: every ds_write_b128 covers 1 KB of consecutive addresses (conflict-free)
 #pragma unroll
   for (int j = 0; j < BPL / 4; ++j)
@@ -406,7 +443,18 @@ __device__ __forceinline__ int binsort_histogram_full(const float (&key)[EPT], i
     __builtin_amdgcn_sched_barrier(0);
   }
   __builtin_amdgcn_wave_barrier();
-  return binsort_scan<BPL>(cnt, lane) >> 2;              // the largest counter, counted in bytes: four per key
+  if constexpr (NB == binsort_bins<EPT>()) {
+    return binsort_scan<BPL>(cnt, lane) >> 2;            // the largest counter, counted in bytes: four per key
+  } else {
+    unsigned total;
+    const int g = binsort_scan_sum_first<BPL>(cnt, lane, total) >> 2;
+    // Where 4 NB is no power of two the mask of binsort_off lets the low bits of a NaN name a word behind the last
+    // counter (every key in [0, 1] stays below 4 NB; the mask stays inside the wave's block: wave_sort_binned).  Such a
+    // key is missing from the sum over the NB counters: the slice takes the network, which needs no counter, before any
+    // key has moved.
+    if constexpr (!is_pow2(NB)) return total == 256u * EPT ? g : SHW_BINSORT_MAX_RUN + 1;
+    return g;
+  }
 }
 
 // Steps 3-5 of a full class (only after binsort_histogram_full returned g <= SHW_BINSORT_MAX_RUN).  The byte position of
@@ -429,6 +477,26 @@ __device__ __forceinline__ void binsort_place_full(float (&key)[EPT], const unsi
   }
   __builtin_amdgcn_wave_barrier();
   binsort_read_back_and_fix<EPT, REM_FIRST>(key, lane, g, buf);
+}
+
+// The placement in two steps, for counters that lie UNDER the staging buffer (the headline loss kernel: wave_sort_binned,
+// ALIAS_BPL): all EPT atomics first, their byte positions kept in the registers that held the counters' addresses, then
+// the EPT writes.  Nothing reads a counter after the last atomic, so the first write may land on one.  LDS operations of one
+// wave execute in order; the compiler is held to the same order by the memory clobber and the scheduling barrier between
+// the steps (an atomic on `unsigned` and a store of `float` do not alias by their types).  Always REM_FIRST.
+template <int EPT>
+__device__ __forceinline__ void binsort_place_full_two_step(float (&key)[EPT], unsigned (&slot)[EPT], int lane, int g,
+                                                            float* buf) {
+  char* bytes = reinterpret_cast<char*>(buf);
+#pragma unroll
+  for (int r = 0; r < EPT; ++r)
+    slot[r] = __hip_atomic_fetch_add(lds_counter(slot[r]), 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r = 0; r < EPT; ++r) *reinterpret_cast<float*>(bytes + binsort_addr4<EPT>(slot[r])) = key[r];
+  __builtin_amdgcn_wave_barrier();
+  binsort_read_back_and_fix<EPT, true>(key, lane, g, buf);
 }
 
 // ---- the classes with pads (n < 64*EPT): the saturating map, counters in keys -----------------------------------------
@@ -574,12 +642,29 @@ __device__ __forceinline__ void wave_sort_relayout(T (&key)[EPT], int lane, T ma
 // scratch: binsort_bins<EPT>() counters with the 64*EPT floats of the staging buffer directly behind them (one block).
 // Returns the longest run of keys that share a bin (> SHW_BINSORT_MAX_RUN: the slice took the network).
 // REM_FIRST (full classes): the phase order of binsort_read_back_and_fix.
-template <int EPT, bool FULL, bool REM_FIRST = false>
+// ALIAS_BPL (full classes with REM_FIRST; 0: off): 64 * ALIAS_BPL counters that start at `scratch` as always and run on
+// UNDER the staging buffer, which stays where it is, binsort_bins<EPT>() floats in: the block is no larger, the bins may be
+// up to three times as many.  The counters are dead before the first key is written (binsort_place_full_two_step), and the
+// caller's next sort zeroes them only after this one's read-back.
+template <int EPT, bool FULL, bool REM_FIRST = false, int ALIAS_BPL = 0>
 __device__ __forceinline__ int wave_sort_binned(float (&key)[EPT], int lane, int n, float* scratch, bool rows) {
   unsigned* cnt = reinterpret_cast<unsigned*>(scratch);
   float* buf = scratch + binsort_bins<EPT>();
   int g = SHW_BINSORT_MAX_RUN + 1;
-  if constexpr (FULL) {
+  if constexpr (FULL && ALIAS_BPL != 0) {
+    static_assert(REM_FIRST && ALIAS_BPL % 4 == 0, "counters under the buffer: the headline kernel's form");
+    constexpr int NB = 64 * ALIAS_BPL;
+    // counters [0, 4 NB) and buffer [4 bins, 4 bins + 256 EPT) both end inside the one block of (bins + 64 EPT) floats
+    static_assert(4 * NB <= 4 * (binsort_bins<EPT>() + 64 * EPT), "the counters must end inside the wave's block");
+    // ... and so does whatever word the mask of binsort_off can name for a key that is no number (binsort_histogram_full)
+    static_assert(next_pow2_c(4 * NB) <= 4 * (binsort_bins<EPT>() + 64 * EPT), "the map's mask must stay inside the block");
+    unsigned slot[EPT];
+    if (!rows || binsort_keys_fit<EPT>(key)) g = binsort_histogram_full<EPT, NB>(key, lane, cnt, slot);
+    if (g <= SHW_BINSORT_MAX_RUN) {
+      binsort_place_full_two_step<EPT>(key, slot, lane, g, buf);
+      return g;
+    }
+  } else if constexpr (FULL) {
     unsigned slot[EPT];
     if (!rows || binsort_keys_fit<EPT>(key)) g = binsort_histogram_full<EPT>(key, lane, cnt, slot);
     if (g <= SHW_BINSORT_MAX_RUN) {

@@ -88,6 +88,12 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
   // the executed path; profiles/r23_forward_summary.txt).  Every other class keeps the loop: the general-power kernel
   // <32,1,0,true> is 148 KB of text as it is.
   constexpr bool TWO_PASS = ROLL && PMODE == 2;
+  // ... and its sort's counters lie under the staging buffer: 64 * 20 = 1280 bins in the same 12 KB (bin_sort.hpp,
+  // wave_sort_binned; 0: counters in front of the buffer, 1024 bins, as in every other class).  vbuf and the LDS request do
+  // not move.  20 bins per lane of the scan, measured against 12 .. 36 (profiles/r28_forward_summary.txt): a lane stride of
+  // 80 B keeps the scan's ds_read_b128 free of bank conflicts; 128 B (32 per lane) does not and costs 27 %.
+  constexpr int kAliasBPL = TWO_PASS ? 20 : 0;
+  static_assert(64 * kAliasBPL <= forward_lds_floats(EPT), "the counters must fit the wave's LDS block");
   constexpr int kUnroll = TWO_PASS ? 2 : 1;        // 1: not unrolled
 #pragma unroll kUnroll
   for (int which = 0; which < 2; ++which) {        // 0: source -> registers, 1: target -> LDS
@@ -118,10 +124,10 @@ __global__ __launch_bounds__(WAVES * 64, forward_min_waves(EPT, PMODE, FULL)) vo
     }
 #endif
 #ifdef SHW_DBG_RUNLEN          // developer build (tools/nonuniform_time.py): slice_shift reports the longest equal-bin run
-    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL, TWO_PASS>(key, ln, count, scratch, A.dirs == nullptr));
+    if constexpr (BINS) dbg_run = max(dbg_run, wave_sort_binned<EPT, FULL, TWO_PASS, kAliasBPL>(key, ln, count, scratch, A.dirs == nullptr));
     else wave_sort<EPT>(key, ln);
 #else
-    if constexpr (BINS) wave_sort_binned<EPT, FULL, TWO_PASS>(key, ln, count, scratch, A.dirs == nullptr);
+    if constexpr (BINS) wave_sort_binned<EPT, FULL, TWO_PASS, kAliasBPL>(key, ln, count, scratch, A.dirs == nullptr);
     else wave_sort<EPT>(key, ln);
 #endif
     if (which == 0) {
