@@ -5,8 +5,9 @@
 // in Flow_ellipsoid*.ipynb), which needs equal sample counts.  It is the spherical kernel without the
 // circle: no atan2, no cyclic shift (k = 0), no wrap -- one wavefront per (pair, slice), the same
 // register-resident sort.  Per slice it returns S_l = sum_i |u_(i) - v_(i)|^p; the outer
-// (mean_l S_l)^(1/p) of the notebook is host-side arithmetic on L numbers.
-#include "ssw_common.hpp"
+// (mean_l S_l)^(1/p) of the notebook is host-side arithmetic on L numbers.  The forward kernel is the shared body
+// euclid_forward (euclid_common.hpp) with the R^3 projection as its key.
+#include "euclid_common.hpp"
 
 namespace shw {
 
@@ -24,95 +25,34 @@ struct EswArgs {
   int num_groups;
 };
 
-// projections of one cloud on one direction; padding keys are +inf
-template <int EPT>
-__device__ __forceinline__ void load_projections(const float* __restrict__ X, int count, int lane,
-                                                 float tx, float ty, float tz, float (&key)[EPT]) {
-  constexpr int CH = EPT < 8 ? EPT : 8;
-#pragma unroll
-  for (int r0 = 0; r0 < EPT; r0 += CH) {
-    float px[CH], py[CH], pz[CH];
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int i = min((r0 + j) * kWave + lane, count - 1);
-      px[j] = X[3 * i]; py[j] = X[3 * i + 1]; pz[j] = X[3 * i + 2];
-    }
-#pragma unroll
-    for (int j = 0; j < CH; ++j) {
-      const int i = (r0 + j) * kWave + lane;
-      const float d = fmaf(pz[j], tz, fmaf(py[j], ty, px[j] * tx));
-      key[r0 + j] = (i < count) ? d : __builtin_inff();
-    }
-    __builtin_amdgcn_sched_barrier(0);
+// the key of a point is its projection on the slice's direction; the coefficient is the derivative itself
+struct EswKey {
+  static constexpr bool kRolledGeneralP = false;
+  using row_t = int;       // pairs * slices, as the entry computes it
+  const float *xs, *xt, *thetas;
+  long theta_pair_stride;
+  int slices;
+  long cloud;              // offset of the pair's clouds
+  float tx, ty, tz;
+  __device__ __forceinline__ void begin_row(int s, int n) {
+    const int b = s / slices, l = s - b * slices;
+    const float* T = thetas + (long)b * theta_pair_stride + (long)l * 3;
+    tx = T[0]; ty = T[1]; tz = T[2];
+    cloud = (long)b * n * 3;
   }
-}
+  template <int EPT>
+  __device__ __forceinline__ void load(int which, int, int n, int lane, float (&key)[EPT]) const {
+    load_projections<EPT>((which == 0 ? xt : xs) + cloud, n, lane, tx, ty, tz, key);
+  }
+  template <bool NEG>
+  static __device__ __forceinline__ float coef(float g, float) { return NEG ? -g : g; }
+};
 
 template <int EPT, int WAVES, int PMODE, bool GRAD>
 __global__ __launch_bounds__(WAVES * 64) void esw_kernel(EswArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int ROW = EPT * kWave;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  float* vbuf = lds + wave * ((GRAD ? 2 : 1) * ROW);
-  int* vidx = reinterpret_cast<int*>(vbuf + ROW);            // GRAD only
-
-  const int vid = xcd_contiguous_id(blockIdx.x, A.num_groups);
-  const int s = vid * WAVES + wave;
-  if (s >= A.pairs * A.slices) return;
-  const int b = s / A.slices, l = s - b * A.slices;
-  const int n = A.n;
-  const float* T = A.thetas + (long)b * A.theta_pair_stride + (long)l * 3;
-  const float tx = T[0], ty = T[1], tz = T[2];
-
-  float u[EPT];
-  int uidx[EPT];
-#pragma nounroll
-  for (int which = 0; which < 2; ++which) {
-    const float* X = (which == 0 ? A.xt : A.xs) + (long)b * n * 3;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    load_projections<EPT>(X, n, ln, tx, ty, tz, u);
-    if constexpr (GRAD) {
-      item_t item[EPT];
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) item[r] = make_item(orderable(u[r]), r * kWave + ln);
-      wave_sort_kv<EPT>(item, ln);
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) {
-        u[r] = from_orderable(item_key(item[r]));
-        uidx[r] = item_idx(item[r]);
-      }
-    } else {
-      wave_sort<EPT>(u, ln);
-    }
-    if (which == 0) {
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) {
-        vbuf[r * kWave + lane] = u[r];
-        if constexpr (GRAD) vidx[r * kWave + lane] = uidx[r];
-      }
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-
-  float acc = 0.f;
-  float* cs = GRAD ? A.coef_s + (long)s * n : nullptr;
-  float* ct = GRAD ? A.coef_t + (long)s * n : nullptr;
-#pragma unroll
-  for (int r = 0; r < EPT; ++r) {
-    const int e = lane * EPT + r;                            // sorted position; target e sits in the same slot
-    const float d = u[r] - vbuf[r * kWave + lane];
-    if (e < n) {
-      acc += pow_abs<PMODE>(d, A.p, A.p_int);
-      if constexpr (GRAD) {
-        const float g = dpow_abs<PMODE>(d, A.p, A.p_int);
-        cs[uidx[r]] = g;
-        ct[vidx[r * kWave + lane]] = -g;
-      }
-    }
-  }
-  acc = wave_sum(acc, lane);
-  if (lane == 0) A.slice_sum[s] = acc;
+  euclid_forward<EPT, WAVES, PMODE, GRAD>(EswKey{A.xs, A.xt, A.thetas, A.theta_pair_stride, A.slices},
+                                          A.pairs * A.slices, A.n, A.num_groups, A.p, A.p_int, A.slice_sum,
+                                          A.coef_s, A.coef_t);
 }
 
 // grad[b,i,:] = sum_l w[b,l] * coef[b,l,i] * theta[b,l,:]   (w = upstream gradient of the per-slice sums)
@@ -177,25 +117,6 @@ __global__ __launch_bounds__(256) void esw_backward_dirs_kernel(const float* __r
   }
 }
 
-template <int EPT, int WAVES>
-static int launch_esw(EswArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  const long groups = (total + WAVES - 1) / WAVES;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
-  const bool grad = A.coef_s != nullptr;
-  const size_t lds = (size_t)WAVES * (grad ? 2 : 1) * EPT * kWave * sizeof(float);
-  const dim3 grid((unsigned)groups), block(WAVES * 64);
-  if (A.p_int == 2) {
-    if (grad) hipLaunchKernelGGL((esw_kernel<EPT, WAVES, 2, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((esw_kernel<EPT, WAVES, 2, false>), grid, block, lds, stream, A);
-  } else {
-    if (grad) hipLaunchKernelGGL((esw_kernel<EPT, WAVES, 0, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((esw_kernel<EPT, WAVES, 0, false>), grid, block, lds, stream, A);
-  }
-  return (int)hipGetLastError();
-}
-
 }  // namespace shw
 
 extern "C" {
@@ -204,24 +125,19 @@ int shw_esw_forward(const float* xs, const float* xt, const float* thetas, int p
                     long theta_pair_stride, float p, float* slice_sum, float* coef_s, float* coef_t, void* stream) {
   if (!xs || !xt || !thetas || !slice_sum) return (int)hipErrorInvalidValue;
   if ((coef_s == nullptr) != (coef_t == nullptr)) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || slices < 0 || n < 1 || n > 4096 || !(p >= 1.f)) return (int)hipErrorInvalidValue;
-  if (theta_pair_stride != 0 && theta_pair_stride < (long)slices * 3) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kAnyPairs, pairs, n, n, 3, slices, theta_pair_stride) || !(p >= 1.f))
+    return (int)hipErrorInvalidValue;
   if (pairs == 0 || slices == 0) return 0;
   shw::EswArgs A{};
   A.xs = xs; A.xt = xt; A.thetas = thetas; A.slice_sum = slice_sum; A.coef_s = coef_s; A.coef_t = coef_t;
   A.pairs = pairs; A.n = n; A.slices = slices; A.theta_pair_stride = theta_pair_stride;
   A.p = p; A.p_int = shw::small_integer_power(p);
-  if (p == 1.f) A.p_int = 1;
-  switch (shw::ept_for(n, n)) {
-    case 1: return shw::launch_esw<1, 4>(A, (hipStream_t)stream);
-    case 2: return shw::launch_esw<2, 4>(A, (hipStream_t)stream);
-    case 4: return shw::launch_esw<4, 4>(A, (hipStream_t)stream);
-    case 8: return shw::launch_esw<8, 4>(A, (hipStream_t)stream);
-    case 16: return shw::launch_esw<16, 4>(A, (hipStream_t)stream);
-    case 32: return shw::launch_esw<32, 2>(A, (hipStream_t)stream);
-    case 64: return shw::launch_esw<64, 1>(A, (hipStream_t)stream);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return shw::launch_euclid_forward<shw::EswKey::kRolledGeneralP>(
+      (long)pairs * slices, n, A.p_int, coef_s != nullptr, A.num_groups,
+      [&](auto ept, auto waves, auto pm, auto g, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((shw::esw_kernel<decltype(ept)::value, decltype(waves)::value, decltype(pm)::value,
+                                            decltype(g)::value>), grid, block, lds, (hipStream_t)stream, A);
+      });
 }
 
 int shw_esw_backward_points(const float* thetas, const float* coef_s, const float* coef_t, const float* slice_w,

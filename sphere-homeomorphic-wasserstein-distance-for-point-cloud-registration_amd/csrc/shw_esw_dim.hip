@@ -3,12 +3,11 @@
 // clouds).  Same math as shw_esw.hip with D coordinates per point instead of 3: one wavefront per (pair, slice), the
 // key of point i is sum_d x[i,d] * theta[l,d] accumulated in the order d = 0..D-1 (at D = 3 exactly the expression of
 // shw_esw.hip), then the same register sort, sorted difference and coefficient rows.  The coefficient rows
-// d S_l / d projection do not depend on D; only the projection and the two gradient kernels do.
-#include "esw_project.hpp"   // load_projections_dim: the projection loader, shared with shw_line_ot.hip
+// d S_l / d projection do not depend on D; only the projection and the two gradient kernels do.  The forward kernel is
+// the shared body euclid_forward (euclid_common.hpp) with the D-generic projection as its key.
+#include "euclid_common.hpp"   // load_projections_dim: the projection loader, shared with shw_line_ot.hip
 
 namespace shw {
-
-constexpr int kMaxEswDim = 64;
 
 struct EswDimArgs {
   const float* xs;
@@ -24,110 +23,36 @@ struct EswDimArgs {
   int num_groups;
 };
 
+// the key of a point is its projection on the slice's direction row; the coefficient is the derivative itself
+struct EswDimKey {
+  static constexpr bool kRolledGeneralP = false;
+  using row_t = int;       // pairs * slices, as the entry computes it
+  const float *xs, *xt, *thetas;
+  long theta_pair_stride;
+  int dim, slices;
+  const float* T;          // the slice's direction row
+  long cloud;              // offset of the pair's clouds
+  __device__ __forceinline__ void begin_row(int s, int n) {
+    const int b = s / slices, l = s - b * slices;
+    T = thetas + (long)b * theta_pair_stride + (long)l * dim;
+    cloud = (long)b * n * dim;
+  }
+  template <int EPT>
+  __device__ __forceinline__ void load(int which, int, int n, int lane, float (&key)[EPT]) const {
+    load_projections_dim<EPT>((which == 0 ? xt : xs) + cloud, n, dim, lane, T, key);
+  }
+  template <bool NEG>
+  static __device__ __forceinline__ float coef(float g, float) { return NEG ? -g : g; }
+};
+
 template <int EPT, int WAVES, int PMODE, bool GRAD>
 __global__ __launch_bounds__(WAVES * 64) void esw_dim_kernel(EswDimArgs A) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int ROW = EPT * kWave;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  float* vbuf = lds + wave * ((GRAD ? 2 : 1) * ROW);
-  int* vidx = reinterpret_cast<int*>(vbuf + ROW);            // GRAD only
-
-  const int vid = xcd_contiguous_id(blockIdx.x, A.num_groups);
-  const int s = vid * WAVES + wave;
-  if (s >= A.pairs * A.slices) return;
-  const int b = s / A.slices, l = s - b * A.slices;
-  const int n = A.n, dim = A.dim;
-  const float* T = A.thetas + (long)b * A.theta_pair_stride + (long)l * dim;
-
-  float u[EPT];
-  int uidx[EPT];
-#pragma nounroll
-  for (int which = 0; which < 2; ++which) {
-    const float* X = (which == 0 ? A.xt : A.xs) + (long)b * n * dim;
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    load_projections_dim<EPT>(X, n, dim, ln, T, u);
-    if constexpr (GRAD) {
-      item_t item[EPT];
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) item[r] = make_item(orderable(u[r]), r * kWave + ln);
-      wave_sort_kv<EPT>(item, ln);
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) {
-        u[r] = from_orderable(item_key(item[r]));
-        uidx[r] = item_idx(item[r]);
-      }
-    } else {
-      wave_sort<EPT>(u, ln);
-    }
-    if (which == 0) {
-#pragma unroll
-      for (int r = 0; r < EPT; ++r) {
-        vbuf[r * kWave + lane] = u[r];
-        if constexpr (GRAD) vidx[r * kWave + lane] = uidx[r];
-      }
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-
-  float acc = 0.f;
-  float* cs = GRAD ? A.coef_s + (long)s * n : nullptr;
-  float* ct = GRAD ? A.coef_t + (long)s * n : nullptr;
-#pragma unroll
-  for (int r = 0; r < EPT; ++r) {
-    const int e = lane * EPT + r;                            // sorted position; target e sits in the same slot
-    const float d = u[r] - vbuf[r * kWave + lane];
-    if (e < n) {
-      acc += pow_abs<PMODE>(d, A.p, A.p_int);
-      if constexpr (GRAD) {
-        const float g = dpow_abs<PMODE>(d, A.p, A.p_int);
-        cs[uidx[r]] = g;
-        ct[vidx[r * kWave + lane]] = -g;
-      }
-    }
-  }
-  acc = wave_sum(acc, lane);
-  if (lane == 0) A.slice_sum[s] = acc;
+  euclid_forward<EPT, WAVES, PMODE, GRAD>(EswDimKey{A.xs, A.xt, A.thetas, A.theta_pair_stride, A.dim, A.slices},
+                                          A.pairs * A.slices, A.n, A.num_groups, A.p, A.p_int, A.slice_sum,
+                                          A.coef_s, A.coef_t);
 }
 
-// grad[b,i,d0+k] = sum_l w[b,l] * coef[b,l,i] * theta[b,l,d0+k], k < DC: one point per lane, DC coordinates per
-// workgroup (blockIdx.z picks the chunk, so D > 16 splits over the grid instead of spilling).  Coordinates past D
-// re-read the last one and are not stored.
-template <int DC>
-__global__ __launch_bounds__(256) void esw_dim_backward_points_kernel(const float* __restrict__ thetas,
-                                                                      const float* __restrict__ coef_s,
-                                                                      const float* __restrict__ coef_t,
-                                                                      const float* __restrict__ slice_w, int n,
-                                                                      int dim, int slices, long theta_pair_stride,
-                                                                      float* __restrict__ grad_xs,
-                                                                      float* __restrict__ grad_xt, int chunks) {
-  const int b = blockIdx.y;
-  const int d0 = blockIdx.z * DC;
-  const bool is_t = (int)blockIdx.x >= chunks;
-  const int chunk = is_t ? blockIdx.x - chunks : blockIdx.x;
-  const int i = chunk * 256 + threadIdx.x;
-  const int ic = min(i, n - 1);
-  const int last = dim - d0 - 1;
-  const float* C = (is_t ? coef_t : coef_s) + (long)b * slices * n;
-  float* G = (is_t ? grad_xt : grad_xs) + (long)b * n * dim + d0;
-  const float* Tb = thetas + (long)b * theta_pair_stride + d0;
-  const float* W = slice_w + (long)b * slices;
-  float g[DC];
-#pragma unroll
-  for (int k = 0; k < DC; ++k) g[k] = 0.f;
-  for (int l = 0; l < slices; ++l) {
-    const float c = C[(long)l * n + ic] * W[l];
-    const float* Tl = Tb + (long)l * dim;
-#pragma unroll
-    for (int k = 0; k < DC; ++k) g[k] = fmaf(c, Tl[min(k, last)], g[k]);
-  }
-  if (i < n) {
-#pragma unroll
-    for (int k = 0; k < DC; ++k)
-      if (k <= last) G[(long)i * dim + k] = g[k];
-  }
-}
+// (the points gradient is line_esw_backward_points_kernel of shw_line_ot.hip with m = n: launch_line_esw_backward_points)
 
 // grad_theta[b,l,d0+k] = w[b,l] * sum_i ( coef_s[b,l,i] * xs[b,i,d0+k] + coef_t[b,l,i] * xt[b,i,d0+k] ), k < DC:
 // one workgroup per (slice, pair, coordinate chunk), each lane a strided run of points, then the fixed-order tree of
@@ -173,28 +98,6 @@ __global__ __launch_bounds__(256) void esw_dim_backward_dirs_kernel(const float*
   }
 }
 
-template <int EPT, int WAVES>
-static int launch_esw_dim(EswDimArgs& A, hipStream_t stream) {
-  const long total = (long)A.pairs * A.slices;
-  const long groups = (total + WAVES - 1) / WAVES;
-  if (groups > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  A.num_groups = (int)groups;
-  const bool grad = A.coef_s != nullptr;
-  const size_t lds = (size_t)WAVES * (grad ? 2 : 1) * EPT * kWave * sizeof(float);
-  const dim3 grid((unsigned)groups), block(WAVES * 64);
-  if (A.p_int == 2) {
-    if (grad) hipLaunchKernelGGL((esw_dim_kernel<EPT, WAVES, 2, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((esw_dim_kernel<EPT, WAVES, 2, false>), grid, block, lds, stream, A);
-  } else {
-    if (grad) hipLaunchKernelGGL((esw_dim_kernel<EPT, WAVES, 0, true>), grid, block, lds, stream, A);
-    else hipLaunchKernelGGL((esw_dim_kernel<EPT, WAVES, 0, false>), grid, block, lds, stream, A);
-  }
-  return (int)hipGetLastError();
-}
-
-// coordinates per workgroup of the two gradient kernels: 4, 8, or 16 with the rest of D split over blockIdx.z
-inline int coord_chunk(int dim) { return dim <= 4 ? 4 : dim <= 8 ? 8 : 16; }
-
 }  // namespace shw
 
 extern "C" {
@@ -203,78 +106,41 @@ int shw_esw_forward_dim(const float* xs, const float* xt, const float* thetas, i
                         long theta_pair_stride, float p, float* slice_sum, float* coef_s, float* coef_t, void* stream) {
   if (!xs || !xt || !thetas || !slice_sum) return (int)hipErrorInvalidValue;
   if ((coef_s == nullptr) != (coef_t == nullptr)) return (int)hipErrorInvalidValue;
-  if (dim < 1 || dim > shw::kMaxEswDim) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || slices < 0 || n < 1 || n > 4096 || !(p >= 1.f)) return (int)hipErrorInvalidValue;
-  if (theta_pair_stride != 0 && theta_pair_stride < (long)slices * dim) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kAnyPairs, pairs, n, n, dim, slices, theta_pair_stride) || !(p >= 1.f))
+    return (int)hipErrorInvalidValue;
   if (pairs == 0 || slices == 0) return 0;
   shw::EswDimArgs A{};
   A.xs = xs; A.xt = xt; A.thetas = thetas; A.slice_sum = slice_sum; A.coef_s = coef_s; A.coef_t = coef_t;
   A.pairs = pairs; A.n = n; A.dim = dim; A.slices = slices; A.theta_pair_stride = theta_pair_stride;
   A.p = p; A.p_int = shw::small_integer_power(p);
-  if (p == 1.f) A.p_int = 1;
-  switch (shw::ept_for(n, n)) {
-    case 1: return shw::launch_esw_dim<1, 4>(A, (hipStream_t)stream);
-    case 2: return shw::launch_esw_dim<2, 4>(A, (hipStream_t)stream);
-    case 4: return shw::launch_esw_dim<4, 4>(A, (hipStream_t)stream);
-    case 8: return shw::launch_esw_dim<8, 4>(A, (hipStream_t)stream);
-    case 16: return shw::launch_esw_dim<16, 4>(A, (hipStream_t)stream);
-    case 32: return shw::launch_esw_dim<32, 2>(A, (hipStream_t)stream);
-    case 64: return shw::launch_esw_dim<64, 1>(A, (hipStream_t)stream);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return shw::launch_euclid_forward<shw::EswDimKey::kRolledGeneralP>(
+      (long)pairs * slices, n, A.p_int, coef_s != nullptr, A.num_groups,
+      [&](auto ept, auto waves, auto pm, auto g, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((shw::esw_dim_kernel<decltype(ept)::value, decltype(waves)::value, decltype(pm)::value,
+                                                decltype(g)::value>), grid, block, lds, (hipStream_t)stream, A);
+      });
 }
 
 int shw_esw_backward_points_dim(const float* thetas, const float* coef_s, const float* coef_t, const float* slice_w,
                                 int pairs, int n, int dim, int slices, long theta_pair_stride, float* grad_xs,
                                 float* grad_xt, void* stream) {
   if (!thetas || !coef_s || !coef_t || !slice_w || !grad_xs || !grad_xt) return (int)hipErrorInvalidValue;
-  if (dim < 1 || dim > shw::kMaxEswDim) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || pairs > 65535 || slices < 0 || n < 1 || n > 4096) return (int)hipErrorInvalidValue;
-  if (theta_pair_stride != 0 && theta_pair_stride < (long)slices * dim) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kGridYPairs, pairs, n, n, dim, slices, theta_pair_stride)) return (int)hipErrorInvalidValue;
   if (pairs == 0) return 0;
-  const int chunks = (n + 255) / 256;
-  const int dc = shw::coord_chunk(dim);
-  const dim3 grid(2 * chunks, pairs, (dim + dc - 1) / dc), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (dc) {
-    case 4:
-      hipLaunchKernelGGL(shw::esw_dim_backward_points_kernel<4>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w, n,
-                         dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks);
-      break;
-    case 8:
-      hipLaunchKernelGGL(shw::esw_dim_backward_points_kernel<8>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w, n,
-                         dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks);
-      break;
-    default:
-      hipLaunchKernelGGL(shw::esw_dim_backward_points_kernel<16>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w,
-                         n, dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks);
-  }
-  return (int)hipGetLastError();
+  return shw::launch_line_esw_backward_points(thetas, coef_s, coef_t, slice_w, pairs, n, n, dim, slices, theta_pair_stride,
+                                              grad_xs, grad_xt, (hipStream_t)stream);
 }
 
 int shw_esw_backward_dirs_dim(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
                               const float* slice_w, int pairs, int n, int dim, int slices, float* grad_thetas,
                               void* stream) {
   if (!xs || !xt || !coef_s || !coef_t || !slice_w || !grad_thetas) return (int)hipErrorInvalidValue;
-  if (dim < 1 || dim > shw::kMaxEswDim) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || pairs > 65535 || slices < 0 || n < 1 || n > 4096) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kGridYPairs, pairs, n, n, dim, slices, 0)) return (int)hipErrorInvalidValue;
   if (pairs == 0 || slices == 0) return 0;
-  const int dc = shw::coord_chunk(dim);
-  const dim3 grid(slices, pairs, (dim + dc - 1) / dc), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (dc) {
-    case 4:
-      hipLaunchKernelGGL(shw::esw_dim_backward_dirs_kernel<4>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n,
-                         dim, slices, grad_thetas);
-      break;
-    case 8:
-      hipLaunchKernelGGL(shw::esw_dim_backward_dirs_kernel<8>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n,
-                         dim, slices, grad_thetas);
-      break;
-    default:
-      hipLaunchKernelGGL(shw::esw_dim_backward_dirs_kernel<16>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n,
-                         dim, slices, grad_thetas);
-  }
+  shw::with_coord_chunk(dim, [&](auto dc, unsigned z) {
+    hipLaunchKernelGGL(shw::esw_dim_backward_dirs_kernel<decltype(dc)::value>, dim3(slices, pairs, z), dim3(256), 0,
+                       (hipStream_t)stream, xs, xt, coef_s, coef_t, slice_w, n, dim, slices, grad_thetas);
+  });
   return (int)hipGetLastError();
 }
 

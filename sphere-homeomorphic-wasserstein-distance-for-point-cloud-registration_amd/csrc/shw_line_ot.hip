@@ -51,12 +51,10 @@
 // enters the sums with one jump and leaves with the next, the same float both times, so in double it cancels exactly and
 // the atoms that carry mass do not see it.  For the same reason the parked float32 prefix is taken relative to the
 // lane's first cost, which may be such an atom's.
-#include "esw_project.hpp"
+#include "euclid_common.hpp"
 
 namespace shw {
 
-constexpr int kMaxLineDim = 64;
-constexpr int kMaxLinePoints = 4096;
 
 struct LineArgs {
   const float* a;          // rows: u (rows, n); fused: xs (pairs, n, dim)
@@ -98,6 +96,8 @@ __device__ __forceinline__ int line_end(const LineSide& S, int i) {
   else return S.cdf[line_slot(i, S.log_e)];
 }
 
+// (The register half below is sort_keys of euclid_common.hpp written out.  It stays written out on purpose: over
+// load_row_keys + sort_keys the line kernels compile to another schedule, 0.5 .. 1.4 % slower -- profiles/r29_euclid_refactor.txt.)
 // keys of one side (rows form or fused), sorted, into LDS.  IDX: with their original indices ((orderable key, index)
 // items); a value-only call with uniform weights needs none and sorts bare keys, as the equal-size kernels do.
 template <int E, bool IDX>
@@ -498,8 +498,10 @@ __global__ __launch_bounds__(256) void line_weight_reduce_kernel(const float* __
   if (i < count) grad[(long)blockIdx.y * count + i] = g;
 }
 
-// grad[b,i,d0+k] = sum_l w[b,l] * coef[b,l,i] * theta[b,l,d0+k], k < DC: esw_dim_backward_points_kernel with a point
-// count per cloud: the first chunks_s workgroups of a pair serve the n source points, the rest the m target points.
+// grad[b,i,d0+k] = sum_l w[b,l] * coef[b,l,i] * theta[b,l,d0+k], k < DC: one point per lane, DC coordinates per
+// workgroup (blockIdx.z picks the chunk, so D > 16 splits over the grid instead of spilling); the first chunks_s
+// workgroups of a pair serve the n source points, the rest the m target points.  Coordinates past D re-read the last
+// one and are not stored.
 template <int DC>
 __global__ __launch_bounds__(256) void line_esw_backward_points_kernel(const float* __restrict__ thetas,
                                                                        const float* __restrict__ coef_s,
@@ -629,42 +631,30 @@ static int launch_line_class(LineArgs& A, hipStream_t stream, float* pot_a = nul
   A.p_int = small_integer_power(A.p);
   if (pot_a || pot_b) {
     LinePotArgs P{A, pot_a, pot_b};
-    switch (ea > eb ? ea : eb) {
-      case 1: return launch_line_pot<1, 4>(P, stream);
-      case 2: return launch_line_pot<2, 4>(P, stream);
-      case 4: return launch_line_pot<4, 4>(P, stream);
-      case 8: return launch_line_pot<8, 4>(P, stream);
-      case 16: return launch_line_pot<16, 4>(P, stream);
-      case 32: return launch_line_pot<32, 2>(P, stream);
-      case 64: return launch_line_pot<64, 1>(P, stream);
-      default: return (int)hipErrorInvalidValue;
-    }
+    return with_ept_waves(ea > eb ? ea : eb, [&](auto maxe, auto waves) {
+      return launch_line_pot<decltype(maxe)::value, decltype(waves)::value>(P, stream);
+    });
   }
-  switch (ea > eb ? ea : eb) {
-    case 1: return launch_line<1, 4>(A, stream);
-    case 2: return launch_line<2, 4>(A, stream);
-    case 4: return launch_line<4, 4>(A, stream);
-    case 8: return launch_line<8, 4>(A, stream);
-    case 16: return launch_line<16, 4>(A, stream);
-    case 32: return launch_line<32, 2>(A, stream);
-    case 64: return launch_line<64, 1>(A, stream);
-    default: return (int)hipErrorInvalidValue;
-  }
+  return with_ept_waves(ea > eb ? ea : eb, [&](auto maxe, auto waves) {
+    return launch_line<decltype(maxe)::value, decltype(waves)::value>(A, stream);
+  });
 }
 
-inline bool line_counts_ok(int n, int m) { return n >= 1 && n <= kMaxLinePoints && m >= 1 && m <= kMaxLinePoints; }
-
-inline bool line_esw_sizes_ok(int pairs, int n, int m, int dim, int slices, long theta_pair_stride) {
-  if (dim < 1 || dim > kMaxLineDim || !line_counts_ok(n, m)) return false;
-  if (pairs < 0 || pairs > 65535 || slices < 0) return false;
-  if (theta_pair_stride != 0 && theta_pair_stride < (long)slices * dim) return false;
-  return true;
-}
+inline bool line_counts_ok(int n, int m) { return n >= 1 && n <= kMaxEuclidPoints && m >= 1 && m <= kMaxEuclidPoints; }
 
 inline bool line_weights_ok(const float* w, long stride, int count) { return stride == 0 || (w && stride >= count); }
 
-// coordinates per workgroup of the two gradient kernels: 4, 8, or 16 with the rest of D split over blockIdx.z
-inline int line_coord_chunk(int dim) { return dim <= 4 ? 4 : dim <= 8 ? 8 : 16; }
+int launch_line_esw_backward_points(const float* thetas, const float* coef_s, const float* coef_t, const float* slice_w,
+                                    int pairs, int n, int m, int dim, int slices, long theta_pair_stride, float* grad_xs,
+                                    float* grad_xt, hipStream_t stream) {
+  const int chunks_s = (n + 255) / 256, chunks_t = (m + 255) / 256;
+  with_coord_chunk(dim, [&](auto dc, unsigned z) {
+    hipLaunchKernelGGL(line_esw_backward_points_kernel<decltype(dc)::value>, dim3(chunks_s + chunks_t, pairs, z), dim3(256), 0,
+                       stream, thetas, coef_s, coef_t, slice_w, n, m, dim, slices, theta_pair_stride, grad_xs, grad_xt,
+                       chunks_s);
+  });
+  return (int)hipGetLastError();
+}
 
 // the two forward entries, with or without potential rows
 static int line_rows_forward(const float* u, const float* v, long rows, int n, int m, float p, const float* u_weights,
@@ -691,7 +681,8 @@ static int line_esw_forward(const float* xs, const float* xt, const float* theta
   if (!xs || !xt || !thetas || !slice_cost) return (int)hipErrorInvalidValue;
   if ((coef_s == nullptr) != (coef_t == nullptr)) return (int)hipErrorInvalidValue;
   if ((pot_u && !u_weights) || (pot_v && !v_weights)) return (int)hipErrorInvalidValue;
-  if (!line_esw_sizes_ok(pairs, n, m, dim, slices, theta_pair_stride) || !(p >= 1.f)) return (int)hipErrorInvalidValue;
+  if (!euclid_sizes_ok(kGridYPairs, pairs, n, m, dim, slices, theta_pair_stride) || !(p >= 1.f))
+    return (int)hipErrorInvalidValue;
   if (!line_weights_ok(u_weights, u_weight_stride, n) || !line_weights_ok(v_weights, v_weight_stride, m))
     return (int)hipErrorInvalidValue;
   if (pairs == 0 || slices == 0) return 0;
@@ -752,7 +743,7 @@ size_t shw_line_weight_grads_workspace_bytes(int pairs, int slices, int count, i
 int shw_line_weight_grads(const float* pot, const float* slice_w, int pairs, int slices, int count, int shared,
                           void* workspace, float* grad, void* stream) {
   if (!pot || !slice_w || !grad) return (int)hipErrorInvalidValue;
-  if (pairs < 0 || pairs > 65535 || slices < 0 || count < 1 || count > shw::kMaxLinePoints) return (int)hipErrorInvalidValue;
+  if (pairs < 0 || pairs > 65535 || slices < 0 || count < 1 || count > shw::kMaxEuclidPoints) return (int)hipErrorInvalidValue;
   const long rows = (long)pairs * slices;
   if (rows > 0x7fffffffL) return (int)hipErrorInvalidValue;
   if (pairs == 0) return 0;
@@ -786,50 +777,22 @@ int shw_line_esw_backward_points(const float* thetas, const float* coef_s, const
                                  int pairs, int n, int m, int dim, int slices, long theta_pair_stride, float* grad_xs,
                                  float* grad_xt, void* stream) {
   if (!thetas || !coef_s || !coef_t || !slice_w || !grad_xs || !grad_xt) return (int)hipErrorInvalidValue;
-  if (!shw::line_esw_sizes_ok(pairs, n, m, dim, slices, theta_pair_stride)) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kGridYPairs, pairs, n, m, dim, slices, theta_pair_stride)) return (int)hipErrorInvalidValue;
   if (pairs == 0) return 0;
-  const int chunks_s = (n + 255) / 256, chunks_t = (m + 255) / 256;
-  const int dc = shw::line_coord_chunk(dim);
-  const dim3 grid(chunks_s + chunks_t, pairs, (dim + dc - 1) / dc), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (dc) {
-    case 4:
-      hipLaunchKernelGGL(shw::line_esw_backward_points_kernel<4>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w, n,
-                         m, dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks_s);
-      break;
-    case 8:
-      hipLaunchKernelGGL(shw::line_esw_backward_points_kernel<8>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w, n,
-                         m, dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks_s);
-      break;
-    default:
-      hipLaunchKernelGGL(shw::line_esw_backward_points_kernel<16>, grid, block, 0, st, thetas, coef_s, coef_t, slice_w,
-                         n, m, dim, slices, theta_pair_stride, grad_xs, grad_xt, chunks_s);
-  }
-  return (int)hipGetLastError();
+  return shw::launch_line_esw_backward_points(thetas, coef_s, coef_t, slice_w, pairs, n, m, dim, slices, theta_pair_stride,
+                                              grad_xs, grad_xt, (hipStream_t)stream);
 }
 
 int shw_line_esw_backward_dirs(const float* xs, const float* xt, const float* coef_s, const float* coef_t,
                                const float* slice_w, int pairs, int n, int m, int dim, int slices, float* grad_thetas,
                                void* stream) {
   if (!xs || !xt || !coef_s || !coef_t || !slice_w || !grad_thetas) return (int)hipErrorInvalidValue;
-  if (!shw::line_esw_sizes_ok(pairs, n, m, dim, slices, 0)) return (int)hipErrorInvalidValue;
+  if (!shw::euclid_sizes_ok(shw::kGridYPairs, pairs, n, m, dim, slices, 0)) return (int)hipErrorInvalidValue;
   if (pairs == 0 || slices == 0) return 0;
-  const int dc = shw::line_coord_chunk(dim);
-  const dim3 grid(slices, pairs, (dim + dc - 1) / dc), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (dc) {
-    case 4:
-      hipLaunchKernelGGL(shw::line_esw_backward_dirs_kernel<4>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n, m,
-                         dim, slices, grad_thetas);
-      break;
-    case 8:
-      hipLaunchKernelGGL(shw::line_esw_backward_dirs_kernel<8>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n, m,
-                         dim, slices, grad_thetas);
-      break;
-    default:
-      hipLaunchKernelGGL(shw::line_esw_backward_dirs_kernel<16>, grid, block, 0, st, xs, xt, coef_s, coef_t, slice_w, n,
-                         m, dim, slices, grad_thetas);
-  }
+  shw::with_coord_chunk(dim, [&](auto dc, unsigned z) {
+    hipLaunchKernelGGL(shw::line_esw_backward_dirs_kernel<decltype(dc)::value>, dim3(slices, pairs, z), dim3(256), 0,
+                       (hipStream_t)stream, xs, xt, coef_s, coef_t, slice_w, n, m, dim, slices, grad_thetas);
+  });
   return (int)hipGetLastError();
 }
 

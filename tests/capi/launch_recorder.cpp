@@ -5,9 +5,10 @@
 // include/shw.h: the same source builds against any tree that keeps the C ABI.  Built and compared with
 // tests/golden/dispatch_launches.txt.gz by tests/test_dispatch_cpu.py (which documents the case sets).
 //
-//   launch_recorder <set>      set: all | fwd | grad | fwdgrad | kpl | p1 | bwd     (knobs come from the environment)
+//   launch_recorder <set>      set: all | fwd | grad | fwdgrad | kpl | p1 | bwd | euclid     (knobs come from the environment)
 // stdout: one line per call -- the case, then `K<i> g=<grid x>,<grid y> b=<block x> lds=<bytes>` per launch and the
-//         return code; `K<i> = <mangled name>` is printed when a kernel is first launched.
+//         return code (a grid z other than 1 follows grid y); `K<i> = <mangled name>` is printed when a kernel is first
+//         launched.
 // stderr: `unlaunched <mangled name>` for every registered kernel that no case of this run launched.
 #include <cstdarg>
 #include <cstdint>
@@ -47,8 +48,9 @@ int hipLaunchKernel(const void* f, Dim3 grid, Dim3 block, void**, size_t lds, vo
     it = g_ids.emplace(f, (int)g_ids.size()).first;
     printf("K%d = %s\n", it->second, kernel_names().count(f) ? kernel_names()[f].c_str() : "?");
   }
-  char buf[96];
-  snprintf(buf, sizeof buf, " K%d g=%u,%u b=%u lds=%zu |", it->second, grid.x, grid.y, block.x, lds);
+  char buf[96], z[16] = "";
+  if (grid.z != 1) snprintf(z, sizeof z, ",%u", grid.z);
+  snprintf(buf, sizeof buf, " K%d g=%u,%u%s b=%u lds=%zu |", it->second, grid.x, grid.y, z, block.x, lds);
   g_line += buf;
   return 0;
 }
@@ -173,6 +175,146 @@ static void rest() {
   report(shw_stiefel_frames_f64(fake<double>(0), 257, fake<double>(1), nullptr), "stiefel_frames_f64 count=257");
 }
 
+// The Euclidean sliced family (shw_esw, shw_esw_dim, shw_gsw, shw_line_ot): every entry point over the values at which a
+// step of its launch ladders changes.
+static void euclid() {
+  float *const xs = fake<float>(0), *const xt = fake<float>(1), *const th = fake<float>(2), *const sum = fake<float>(3);
+  float *const cs = fake<float>(5), *const ct = fake<float>(6), *const wu = fake<float>(7), *const wv = fake<float>(8);
+  float *const gs = fake<float>(9), *const gt = fake<float>(10), *const sw = fake<float>(11);
+  float *const pu = fake<float>(12), *const pv = fake<float>(13);
+  const int sizes[] = {1, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097};
+  const int unequal[][2] = {{1200, 900}, {900, 1200}, {4096, 1}, {1, 4096}, {65, 64}, {2049, 300}, {300, 4097}};
+  const int dims[] = {1, 3, 4, 5, 8, 9, 16, 17, 64, 65};
+  const float powers[] = {2.f, 1.f, 1.5f};
+
+  // size classes x power x gradient: the forward kernels (3 pairs x 100 slices, dim 6 where there is one)
+  for (int n : sizes)
+    for (float p : powers)
+      for (int grad = 0; grad < 2; ++grad) {
+        float *const a = grad ? cs : nullptr, *const b = grad ? ct : nullptr;
+        report(shw_esw_forward(xs, xt, th, 3, n, 100, 0, p, sum, a, b, nullptr), "esw_forward n=%d p=%g grad=%d", n, p, grad);
+        report(shw_esw_forward_dim(xs, xt, th, 3, n, 6, 100, 0, p, sum, a, b, nullptr), "esw_forward_dim n=%d p=%g grad=%d", n, p, grad);
+        report(shw_gsw_rows_forward(xs, xt, 300, n, p, sum, a, b, nullptr), "gsw_rows_forward n=%d p=%g grad=%d", n, p, grad);
+        report(shw_gsw_circular_forward(xs, xt, th, 3, n, 6, 100, 0, 1.5f, p, sum, a, b, nullptr),
+               "gsw_circular_forward n=%d p=%g grad=%d", n, p, grad);
+      }
+  // line transport: equal and unequal sizes x power x gradient x weights (none, u only, both) x potentials
+  for (int k = 0; k < (int)(sizeof sizes / sizeof sizes[0] + sizeof unequal / sizeof unequal[0]); ++k) {
+    const int ns = sizeof sizes / sizeof sizes[0];
+    const int n = k < ns ? sizes[k] : unequal[k - ns][0], m = k < ns ? sizes[k] : unequal[k - ns][1];
+    for (float p : powers)
+      for (int grad = 0; grad < 2; ++grad)
+        for (int w = 0; w < 3; ++w)
+          for (int pot = 0; pot < 2; ++pot) {
+            float *const a = grad ? cs : nullptr, *const b = grad ? ct : nullptr;
+            const float *const u_w = w ? wu : nullptr, *const v_w = w == 2 ? wv : nullptr;
+            const long us = w ? n : 0, vs = w == 2 ? m : 0;
+            if (!pot) {
+              report(shw_line_rows_forward(xs, xt, 300, n, m, p, u_w, v_w, us, vs, sum, a, b, nullptr),
+                     "line_rows_forward n=%d m=%d p=%g grad=%d weights=%d", n, m, p, grad, w);
+              report(shw_line_esw_forward(xs, xt, th, 3, n, m, 6, 100, 0, p, u_w, v_w, us, vs, sum, a, b, nullptr),
+                     "line_esw_forward n=%d m=%d p=%g grad=%d weights=%d", n, m, p, grad, w);
+            } else {                                            // (a potential row without its weights: refused)
+              report(shw_line_rows_forward_pot(xs, xt, 300, n, m, p, u_w, v_w, us, vs, sum, a, b, pu, w == 1 ? nullptr : pv, nullptr),
+                     "line_rows_forward_pot n=%d m=%d p=%g grad=%d weights=%d", n, m, p, grad, w);
+              report(shw_line_esw_forward_pot(xs, xt, th, 3, n, m, 6, 100, 0, p, u_w, v_w, us, vs, sum, a, b, pu,
+                                              w == 1 ? nullptr : pv, nullptr),
+                     "line_esw_forward_pot n=%d m=%d p=%g grad=%d weights=%d", n, m, p, grad, w);
+            }
+          }
+  }
+  // the gradient kernels over the point counts (workgroups of 256 points)
+  for (int n : sizes) {
+    report(shw_esw_backward_points(th, cs, ct, sw, 2, n, 100, 0, gs, gt, nullptr), "esw_backward_points n=%d", n);
+    report(shw_esw_backward_dirs(xs, xt, cs, ct, sw, 2, n, 100, gs, nullptr), "esw_backward_dirs n=%d", n);
+    report(shw_esw_backward_points_dim(th, cs, ct, sw, 2, n, 6, 100, 0, gs, gt, nullptr), "esw_backward_points_dim n=%d", n);
+    report(shw_esw_backward_dirs_dim(xs, xt, cs, ct, sw, 2, n, 6, 100, gs, nullptr), "esw_backward_dirs_dim n=%d", n);
+    report(shw_gsw_circular_backward_points(xs, xt, th, cs, ct, sw, 2, n, 6, 100, 0, 1.5f, gs, gt, nullptr),
+           "gsw_circular_backward_points n=%d", n);
+    report(shw_gsw_circular_backward_dirs(xs, xt, th, cs, ct, sw, 2, n, 6, 100, 0, 1.5f, gs, nullptr),
+           "gsw_circular_backward_dirs n=%d", n);
+  }
+  for (const auto& nm : unequal) {
+    report(shw_line_esw_backward_points(th, cs, ct, sw, 2, nm[0], nm[1], 6, 100, 0, gs, gt, nullptr),
+           "line_esw_backward_points n=%d m=%d", nm[0], nm[1]);
+    report(shw_line_esw_backward_dirs(xs, xt, cs, ct, sw, 2, nm[0], nm[1], 6, 100, gs, nullptr),
+           "line_esw_backward_dirs n=%d m=%d", nm[0], nm[1]);
+  }
+  // point dimension (coordinate chunks of the gradient kernels) x stride of the directions: shared, per pair, too short
+  for (int dim : dims)
+    for (int st = 0; st < 3; ++st) {
+      const long stride = st == 0 ? 0 : 100L * dim - (st == 2);
+      for (int grad = 0; grad < 2; ++grad) {
+        float *const a = grad ? cs : nullptr, *const b = grad ? ct : nullptr;
+        report(shw_esw_forward_dim(xs, xt, th, 2, 1200, dim, 100, stride, 2.f, sum, a, b, nullptr),
+               "esw_forward_dim dim=%d stride=%ld grad=%d", dim, stride, grad);
+        report(shw_gsw_circular_forward(xs, xt, th, 2, 1200, dim, 100, stride, 1.5f, 2.f, sum, a, b, nullptr),
+               "gsw_circular_forward dim=%d stride=%ld grad=%d", dim, stride, grad);
+        report(shw_line_esw_forward(xs, xt, th, 2, 1200, 900, dim, 100, stride, 2.f, nullptr, nullptr, 0, 0, sum, a, b, nullptr),
+               "line_esw_forward dim=%d stride=%ld grad=%d", dim, stride, grad);
+      }
+      report(shw_esw_backward_points_dim(th, cs, ct, sw, 2, 1200, dim, 100, stride, gs, gt, nullptr),
+             "esw_backward_points_dim dim=%d stride=%ld", dim, stride);
+      report(shw_gsw_circular_backward_points(xs, xt, th, cs, ct, sw, 2, 1200, dim, 100, stride, 1.5f, gs, gt, nullptr),
+             "gsw_circular_backward_points dim=%d stride=%ld", dim, stride);
+      report(shw_gsw_circular_backward_dirs(xs, xt, th, cs, ct, sw, 2, 1200, dim, 100, stride, 1.5f, gs, nullptr),
+             "gsw_circular_backward_dirs dim=%d stride=%ld", dim, stride);
+      report(shw_line_esw_backward_points(th, cs, ct, sw, 2, 1200, 900, dim, 100, stride, gs, gt, nullptr),
+             "line_esw_backward_points dim=%d stride=%ld", dim, stride);
+      if (st == 0) {
+        report(shw_esw_backward_dirs_dim(xs, xt, cs, ct, sw, 2, 1200, dim, 100, gs, nullptr), "esw_backward_dirs_dim dim=%d", dim);
+        report(shw_line_esw_backward_dirs(xs, xt, cs, ct, sw, 2, 1200, 900, dim, 100, gs, nullptr), "line_esw_backward_dirs dim=%d", dim);
+      }
+    }
+  // problem counts: a grid's y holds 65535 pairs; a forward grid 2^31 - 1 workgroups
+  const int counts[][2] = {{0, 100}, {1, 0}, {1, 1}, {65535, 1}, {65536, 1}, {65536, 32768}, {-1, 1}};      // pairs, slices
+  for (const auto& c : counts) {
+    const int B = c[0], L = c[1];
+    report(shw_esw_forward(xs, xt, th, B, 200, L, 0, 2.f, sum, cs, ct, nullptr), "esw_forward pairs=%d slices=%d", B, L);
+    report(shw_esw_forward_dim(xs, xt, th, B, 200, 6, L, 0, 2.f, sum, cs, ct, nullptr), "esw_forward_dim pairs=%d slices=%d", B, L);
+    report(shw_gsw_rows_forward(xs, xt, (long)B * L, 200, 2.f, sum, cs, ct, nullptr), "gsw_rows_forward rows=%ld", (long)B * L);
+    report(shw_gsw_circular_forward(xs, xt, th, B, 200, 6, L, 0, 1.5f, 2.f, sum, cs, ct, nullptr),
+           "gsw_circular_forward pairs=%d slices=%d", B, L);
+    report(shw_line_rows_forward(xs, xt, (long)B * L, 200, 150, 2.f, nullptr, nullptr, 0, 0, sum, cs, ct, nullptr),
+           "line_rows_forward rows=%ld", (long)B * L);
+    report(shw_line_esw_forward(xs, xt, th, B, 200, 150, 6, L, 0, 2.f, nullptr, nullptr, 0, 0, sum, cs, ct, nullptr),
+           "line_esw_forward pairs=%d slices=%d", B, L);
+    report(shw_line_esw_forward_pot(xs, xt, th, B, 200, 150, 6, L, 0, 2.f, wu, wv, 200, 150, sum, cs, ct, pu, pv, nullptr),
+           "line_esw_forward_pot pairs=%d slices=%d", B, L);
+    report(shw_esw_backward_points(th, cs, ct, sw, B, 200, L, 0, gs, gt, nullptr), "esw_backward_points pairs=%d slices=%d", B, L);
+    report(shw_esw_backward_dirs(xs, xt, cs, ct, sw, B, 200, L, gs, nullptr), "esw_backward_dirs pairs=%d slices=%d", B, L);
+    report(shw_esw_backward_points_dim(th, cs, ct, sw, B, 200, 6, L, 0, gs, gt, nullptr),
+           "esw_backward_points_dim pairs=%d slices=%d", B, L);
+    report(shw_esw_backward_dirs_dim(xs, xt, cs, ct, sw, B, 200, 6, L, gs, nullptr), "esw_backward_dirs_dim pairs=%d slices=%d", B, L);
+    report(shw_gsw_circular_backward_points(xs, xt, th, cs, ct, sw, B, 200, 6, L, 0, 1.5f, gs, gt, nullptr),
+           "gsw_circular_backward_points pairs=%d slices=%d", B, L);
+    report(shw_gsw_circular_backward_dirs(xs, xt, th, cs, ct, sw, B, 200, 6, L, 0, 1.5f, gs, nullptr),
+           "gsw_circular_backward_dirs pairs=%d slices=%d", B, L);
+    report(shw_line_esw_backward_points(th, cs, ct, sw, B, 200, 150, 6, L, 0, gs, gt, nullptr),
+           "line_esw_backward_points pairs=%d slices=%d", B, L);
+    report(shw_line_esw_backward_dirs(xs, xt, cs, ct, sw, B, 200, 150, 6, L, gs, nullptr),
+           "line_esw_backward_dirs pairs=%d slices=%d", B, L);
+  }
+  // refused: a power below 1, one coefficient row without the other, weights with a stride shorter than the row
+  report(shw_esw_forward(xs, xt, th, 3, 200, 100, 0, 0.5f, sum, nullptr, nullptr, nullptr), "esw_forward p=0.5");
+  report(shw_esw_forward_dim(xs, xt, th, 3, 200, 6, 100, 0, 2.f, sum, cs, nullptr, nullptr), "esw_forward_dim coef_s only");
+  report(shw_gsw_rows_forward(xs, xt, 300, 200, 0.5f, sum, nullptr, nullptr, nullptr), "gsw_rows_forward p=0.5");
+  report(shw_gsw_circular_forward(xs, xt, th, 3, 200, 6, 100, 0, 1.5f, 2.f, sum, nullptr, ct, nullptr), "gsw_circular_forward coef_t only");
+  report(shw_line_rows_forward(xs, xt, 300, 200, 150, 2.f, wu, nullptr, 199, 0, sum, nullptr, nullptr, nullptr), "line_rows_forward weight stride 199");
+  report(shw_line_esw_forward(xs, xt, th, 3, 200, 150, 6, 100, 0, 0.5f, nullptr, nullptr, 0, 0, sum, nullptr, nullptr, nullptr), "line_esw_forward p=0.5");
+  // the reduction of the potentials over the slices: per pair, or shared (groups of 64 rows, then the groups)
+  const int reduce[][2] = {{0, 100}, {1, 1}, {1, 64}, {1, 65}, {2, 100}, {65535, 1}, {65536, 1}, {65535, 64}, {65535, 65}};
+  for (const auto& c : reduce)
+    for (int count : {1, 256, 257, 4096, 4097})
+      for (int shared = 0; shared < 2; ++shared)
+        for (int ws = 0; ws < 2; ++ws) {
+          if (ws && !shared) continue;
+          const size_t bytes = shw_line_weight_grads_workspace_bytes(c[0], c[1], count, shared);
+          report(shw_line_weight_grads(pu, sw, c[0], c[1], count, shared, ws ? fake<void>(14) : nullptr, gs, nullptr),
+                 "line_weight_grads pairs=%d slices=%d count=%d shared=%d workspace=%d of %zu", c[0], c[1], count, shared, ws, bytes);
+        }
+}
+
 int main(int argc, char** argv) {
   const std::string set = argc > 1 ? argv[1] : "all";
   if (set == "all") {
@@ -190,14 +332,15 @@ int main(int argc, char** argv) {
     sliced_sweep(true, true, {1.f}, 1); circle(false);
   } else if (set == "bwd") {
     backward();
+  } else if (set == "euclid") {         // the Euclidean sliced family: no knob reaches it
+    euclid();
   } else {
     fprintf(stderr, "unknown case set %s\n", set.c_str());
     return 2;
   }
   for (const auto& kv : kernel_names()) {
     const std::string& name = kv.second;
-    const bool other_unit = name.find("esw_") != std::string::npos || name.find("sinkhorn") != std::string::npos ||
-                            name.find("chamfer") != std::string::npos;
+    const bool other_unit = name.find("sinkhorn") != std::string::npos || name.find("chamfer") != std::string::npos;
     if (!other_unit && !g_ids.count(kv.first)) fprintf(stderr, "unlaunched %s\n", name.c_str());
   }
   return 0;

@@ -5,13 +5,17 @@ tests/capi/launch_recorder.cpp: a stub HIP runtime that records kernel name, gri
 launch, and a driver that calls the C entry points of include/shw.h over the sizes, problem counts, powers and
 pointer alignments at which the selection rules change.  The driver runs once per knob setting, in a fresh process
 each (the knobs are read once), and only over the entry points the knob can affect.  The concatenated output must
-equal the text kept in tests/golden/dispatch_launches.txt.gz byte for byte (505 KB of text, 35 KB compressed; read it
+equal the text kept in tests/golden/dispatch_launches.txt.gz byte for byte (721 KB of text, 47 KB compressed; read it
 with `zcat`): a change of any selection rule, size class, grid or LDS request fails the test, which then prints the
 changed lines as a unified diff.  Together with unchanged device code this proves a host-side refactor
 launch-equivalent without a GPU.
 
-The fixture was recorded from the tree BEFORE the dispatch rules moved into csrc/dispatch.hpp.  To regenerate it from
-any tree that keeps the C ABI (this one by default):
+The fixture was recorded from the tree BEFORE the dispatch rules moved into csrc/dispatch.hpp; its `euclid` section (the
+Euclidean sliced family: shw_esw, shw_esw_dim, shw_gsw, shw_line_ot) from the tree BEFORE their launch ladders moved into
+csrc/euclid_common.hpp, then regenerated once for the one intended change: shw_esw_backward_points_dim launches
+line_esw_backward_points_kernel (same grid, block and LDS).  A kernel is printed as K<i>, numbered by first launch, so
+a renamed kernel renumbers the lines after it: compare with the names put back in.  To regenerate it from any tree that
+keeps the C ABI (this one by default):
 
     python tests/test_dispatch_cpu.py [path/to/tree]
 
@@ -32,7 +36,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 UNITS = ["shw_capi", "shw_ssw_fwd", "shw_ssw_fwd2", "shw_ssw_coop", "shw_ssw_grad", "shw_ssw_grad2", "shw_ssw_grad2_m32",
          "shw_ssw_grad_coop", "shw_ssw_grad_kv", "shw_ssw_p1", "shw_ssw_p1_merge", "shw_ssw_p1_coop", "shw_ssw_general",
-         "shw_ssw_f64", "shw_esw", "shw_esw_dim", "shw_sinkhorn", "shw_chamfer"]
+         "shw_ssw_f64", "shw_esw", "shw_esw_dim", "shw_line_ot", "shw_gsw", "shw_sinkhorn", "shw_chamfer"]
 
 # (knob setting, case set of launch_recorder.cpp): a non-default knob runs over the entry points it can affect
 RUNS = [({}, "all")]
@@ -43,6 +47,7 @@ RUNS += [({"SHW_KPL_CLASSES": "0"}, "kpl")]
 RUNS += [({"SHW_P1_SEARCH_KERNEL": "1"}, "p1")]
 RUNS += [({"SHW_P1_KERNEL": v}, "p1") for v in ("coop", "merge")]
 RUNS += [({"SHW_BWD_WIDE": v}, "bwd") for v in ("0", "2")]
+RUNS += [({}, "euclid")]
 KNOBS = sorted({k for env, _ in RUNS for k in env})
 
 # Registered kernels of the loss units that no case launches, with the reason each cannot be reached in a normal
