@@ -810,6 +810,47 @@ SHW_API int shw_pointnet_backward(const float* x, const float* params, const flo
                                   const float* gfeat, long clouds, long points, int emb, float* gx, float* gparams,
                                   void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The sphere encoder of the phi-max wrappers (csrc/shw_sphere_map.hip).
+ * Replaces: the values and gradients of `transform_to_sphere` (max_spherical_sliced_w.py:334-350) and of
+ * `transform_to_sphere_fast` (max_spherical_sliced_w_fast.py:323-338), the phi both files' `__main__` hand to
+ * `max_spherical_wassersten_distance[_fast]` (:555-561, _fast.py:411-417).  Per point x in R^3:
+ *     z1 = tanh(W1 x + b1),  z2 = tanh(W2 z1 + b2),  o = W3 z2 + b3,
+ *     theta1 = pi (tanh(o0) / 2 + 1/2),  theta2 = pi tanh(o1),
+ *     y = (sin theta1 cos theta2, sin theta1 sin theta2, cos theta1).
+ * PARAMETERS are one flat fp32 buffer in state-dict order: W1 row-major (16, 3), b1 (16), W2 (4, 16), b2 (4), W3 (2, 4),
+ * b3 (2) -- 142 floats.
+ * ENVELOPE: dim == 3, hidden1 == 16, hidden2 == 4.  Finite inputs give finite outputs and gradients: a saturated tanh
+ * is exactly +-1 with a slope of exactly 0.  No entry allocates, synchronises or reads back; all can be captured into a
+ * graph.
+ */
+
+/* 1 for (3, 16, 4), else 0.  Makes no HIP call.  (Replaces the widths written into :338-341, _fast.py:327-329.) */
+SHW_API int shw_sphere_map_supported(int dim, int hidden1, int hidden2);
+
+/* floats of the parameter buffer, 142; 0 outside the envelope.  (The six tensors of `self.net`, :338-342.) */
+SHW_API size_t shw_sphere_map_param_count(int hidden1, int hidden2);
+
+/* workgroups (one wave each) the backward launches for `points` points: min(ceil(points / 64), 1024), 0 for points <= 0.
+ * Workgroup b takes the 64-point tiles b, b + blocks, ... in order.  (No counterpart in the reference: autograd of
+ * :345-348 sums in library order.) */
+SHW_API int shw_sphere_map_backward_blocks(long points);
+
+/* bytes of the backward's workspace, one 142-float partial vector per workgroup; 0 for points <= 0 */
+SHW_API size_t shw_sphere_map_workspace_bytes(long points);
+
+/* x (points, 3) fp32, params (142) fp32 -> y (points, 3) fp32, unit vectors.  points == 0 is a no-op.
+ * (Replaces `forward`, :344-350 and _fast.py:332-338.) */
+SHW_API int shw_sphere_map_forward(const float* x, const float* params, long points, float* y, void* stream);
+
+/* gy (points, 3): gradient w.r.t. y.  gx (points, 3) out, gparams (142) out, laid out as params; either may be NULL and
+ * is then not computed.  Nothing is saved by the forward: the activations are recomputed from x.  workspace:
+ * shw_sphere_map_workspace_bytes bytes, needed only with gparams; it need not be cleared.  gparams is summed without
+ * atomics in a fixed order: the same inputs give the same bits.  points == 0 zeroes gparams.
+ * (Replaces autograd's backward through :345-348, reached from `loss.backward(retain_graph=True)`, :523 and _fast.py:369.) */
+SHW_API int shw_sphere_map_backward(const float* x, const float* params, const float* gy, long points, float* gx,
+                                    float* gparams, float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

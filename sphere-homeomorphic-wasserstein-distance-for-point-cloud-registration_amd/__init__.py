@@ -21,6 +21,7 @@ from .pcrnet import (MLP_Architecture, PCRNet, Pooling, convert2transformation, 
                      pointnet_supported, qrot, quaternion_rotate, quaternion_transform, unpack_pointnet_params)
 from .sinkhorn import (log_N_Sinkhorn_Distance_Loss, log_Sinkhorn_Distance_Loss, sinkhorn_barycentric_map,
                        sinkhorn_pair_costs)
+from .sphere_map import sphere_map, sphere_map_composed, transform_to_sphere, transform_to_sphere_fast
 from .ssw import (binary_search_circle, circle_coordinates, draw_directions, emd1D_circle, enable_float64, enable_float64_general, float64_enabled,
                   float64_general_enabled, max_points_f64, max_points_f64_general, max_sliced_wasserstein_sphere, retract_frames, stiefel_frames, sliced_cost, sliced_wasserstein_sphere, sliced_wasserstein_sphere_fast,
                   ssw_pair_losses)
@@ -39,4 +40,5 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "residual_flow_composed", "residual_flow_supported", "residual_param_count", "MLP_Architecture", "PCRNet",
            "Pooling", "convert2transformation", "create_pose_7d", "get_quaternion", "get_translation",
            "pointnet_max_features", "pointnet_max_features_composed", "pointnet_param_count", "pointnet_supported", "qrot",
-           "quaternion_rotate", "quaternion_transform", "unpack_pointnet_params"]
+           "quaternion_rotate", "quaternion_transform", "unpack_pointnet_params", "sphere_map", "sphere_map_composed",
+           "transform_to_sphere", "transform_to_sphere_fast"]

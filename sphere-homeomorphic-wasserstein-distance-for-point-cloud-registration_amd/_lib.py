@@ -207,6 +207,14 @@ _SIGNATURES = {
     "shw_pointnet_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, ctypes.c_long,
                                              ctypes.c_long, ctypes.c_int, _c_f32p, _c_f32p, ctypes.c_void_p,
                                              ctypes.c_void_p]),
+    # the sphere encoder of the phi-max wrappers (csrc/shw_sphere_map.hip): 3 -> 16 -> 4 -> 2 tanh network, angle map
+    "shw_sphere_map_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_sphere_map_param_count": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
+    "shw_sphere_map_backward_blocks": (ctypes.c_int, [ctypes.c_long]),
+    "shw_sphere_map_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long]),
+    "shw_sphere_map_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, _c_f32p, ctypes.c_void_p]),
+    "shw_sphere_map_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long, _c_f32p, _c_f32p, _c_f32p,
+                                               ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

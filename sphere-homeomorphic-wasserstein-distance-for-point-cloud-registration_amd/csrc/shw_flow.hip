@@ -11,12 +11,14 @@
 // walks the flows forward once, keeping each flow's entry point in LDS (3 floats per flow and lane), then takes the
 // flows last to first, recomputes the flow's layer inputs into LDS (one column per lane, so no barrier and no bank
 // conflict) and back-propagates.  Parameter gradients: a layer's 1 + out*in + out per-lane contributions are summed over
-// the wave 64 at a time by a transpose-reduce (63 adds and 63 cross-lane moves per 64 values, lane L ends with value L),
+// the wave 64 at a time by a transpose-reduce (63 adds and 63 cross-lane moves per 64 values, lane L ends with value L;
+// wave_reduce.hpp, shared with shw_sphere_map.hip),
 // a wave is a block, each block owns one partial vector of the workspace and adds its tiles to it in order, and a second
 // kernel sums the partial vectors in ascending order: no float atomics, the same bits on every run.
 #include <hip/hip_runtime.h>
 
 #include "../../include/shw.h"
+#include "wave_reduce.hpp"
 
 namespace shw {
 
@@ -113,30 +115,6 @@ __global__ __launch_bounds__(kFlowForwardBlock) void flow_forward_kernel(const f
   y[3 * p + 1] = z[1];
   y[3 * p + 2] = z[2];
 }
-
-// N (a power of two, at most 64) per-lane values -> lane L returns the sum over the wave of v[L & (N - 1)].  Step s halves
-// the values: a lane whose bit s is clear keeps the even one of a pair and hands the odd one to its partner, and the other
-// way round; after log2 N steps one value is left and the remaining lane bits are folded by plain exchanges.
-template <int N>
-__device__ __forceinline__ float transpose_reduce(float (&v)[N], int lane) {
-  int s = 0;
-#pragma unroll
-  for (int n = N; n > 1; n >>= 1, ++s) {
-    const bool odd = (lane >> s) & 1;
-#pragma unroll
-    for (int m = 0; m < n / 2; ++m) {
-      const float keep = odd ? v[2 * m + 1] : v[2 * m];
-      const float send = odd ? v[2 * m] : v[2 * m + 1];
-      v[m] = keep + __shfl_xor(send, 1 << s);
-    }
-  }
-  float r = v[0];
-#pragma unroll
-  for (int mask = N; mask < 64; mask <<= 1) r += __shfl_xor(r, mask);
-  return r;
-}
-
-__host__ __device__ constexpr int flow_pow2_ceil(int n) { return n <= 1 ? 1 : 2 * flow_pow2_ceil((n + 1) / 2); }
 
 // the layer's parameter gradients in packed order -- d gamma, d W[j][i] = d[j] a[i], d b[j] = d[j] -- summed over the
 // wave 64 at a time and stored (first tile of the block) or added (later tiles) to the block's partial vector
