@@ -10,7 +10,9 @@ The loop is train_W_COS.py:155-175 (`train_one_epoch`): mean-centre both clouds,
   over points, 5 FC layers 2048->1024->1024->512->512->256 and a 7-d pose head (quaternion + translation),
   `iteration_num = 8` refinements, each one re-embedding the moved source; `--model pcrnet` the package's `shw.PCRNet`
   (the reference's module and state-dict layout) with the trunk and the max-pool on the fused kernels, `--model
-  pcrnet-composed` the same module forced onto its composed torch path, to price the kernels' share of the step;
+  pcrnet-composed` the same module forced onto its composed torch path, to price the kernels' share of the step,
+  `--model pcrnet-fused-pose` `shw.PCRNet` with `fused_head` and `fused_update` set as well: the pose head and the pose
+  update of every refinement on the kernels of csrc/shw_pose.hip;
 * criterion: the live trainer criterion's shape (s2_wasserstein.py:234-262): phi-max inner loop (`phi_max_iter`
   ascent steps with the |norm - 1| regulariser) and the final distance, with the sliced loss `SlicedSphereW` in the
   CSW slot (`--criterion csw`), or the dormant batched wrapper `max_spherical_wassersten_distance_fast`
@@ -118,6 +120,8 @@ def build(slices=512, criterion="csw", phi_max_iter=1, seed=0, dev=None, lr=1e-3
         fused = model == "pcrnet"
         model = shw.PCRNet().to(dev)
         model.feature_model.fused = fused
+    elif model == "pcrnet-fused-pose":
+        model = shw.PCRNet(fused_head=True, fused_update=True).to(dev)
     else:
         raise ValueError(model)
     opt = torch.optim.Adam(model.parameters(), lr=lr, weight_decay=1.4e-8)
@@ -202,7 +206,7 @@ if __name__ == "__main__":
     ap.add_argument("--criterion", default="csw", choices=["csw", "ssw_fast", "plain"])
     ap.add_argument("--phi-max-iter", type=int, default=1)
     ap.add_argument("--phi", default="planar", choices=["planar", "residual", "residual-composed"])
-    ap.add_argument("--model", default="shaped", choices=["shaped", "pcrnet", "pcrnet-composed"])
+    ap.add_argument("--model", default="shaped", choices=["shaped", "pcrnet", "pcrnet-composed", "pcrnet-fused-pose"])
     a = ap.parse_args()
     losses, times = run(a.batch, a.points, a.slices, a.steps, criterion=a.criterion, phi_max_iter=a.phi_max_iter,
                         phi_kind=a.phi, model=a.model)

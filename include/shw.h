@@ -851,6 +851,72 @@ SHW_API int shw_sphere_map_forward(const float* x, const float* params, long poi
 SHW_API int shw_sphere_map_backward(const float* x, const float* params, const float* gy, long points, float* gx,
                                     float* gparams, float* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The registration network after its trunk: the pose head and the rigid pose update (csrc/shw_pose.hip).
+ * Replaces, per refinement iteration of `PCRNet.Pose_estimation` (models/pcrnet.py): `self.linear(torch.cat([template
+ * features, source features], 1))` -- six Linear layers 2 emb -> w1 -> w2 -> w3 -> w4 -> w5 -> 7 with a ReLU after the
+ * first five -- and what follows it: `create_pose_7d`, the transposed rotated identity, the two `bmm`s that update est_R
+ * and est_t, and `quaternion_transform` of the source (data_utils/Data_set_transformation.py).
+ * HEAD PARAMETERS are one flat fp32 buffer: W1 row-major (w1, 2 emb), b1 (w1), W2 (w2, w1), b2, ..., W6 (7, w5), b6 (7).
+ * HEAD ENVELOPE: emb and w1..w5 multiples of 32 in [32, 2048], the output 7 wide, clouds >= 1 (batch tiles of 32 inside
+ * the kernels); no dropout.  Exact f32 on v_mfma_f32_32x32x2_f32, every sum in a fixed order, no atomics: the same
+ * inputs give the same bits.
+ * POSE UPDATE LIMITS: 1 <= clouds <= 65535 (the cloud is gridDim.y), 1 <= points < 2^31.
+ * Anything else is hipErrorInvalidValue, returned before any HIP call.  No entry allocates, synchronises or reads back;
+ * all can be captured into a graph.
+ */
+
+/* 1 inside the head's envelope, else 0.  Makes no HIP call. */
+SHW_API int shw_pose_head_supported(int emb, int w1, int w2, int w3, int w4, int w5);
+
+/* floats of the head's parameter buffer; 0 outside the envelope */
+SHW_API size_t shw_pose_head_param_count(int emb, int w1, int w2, int w3, int w4, int w5);
+
+/* bytes of a head buffer.  which == 0: the forward's workspace (two buffers of partial sums); 1: the backward's; 2: the
+ * saved activations, the five hidden layers after their ReLU stored [feature][clouds rounded up to 32].  0 outside the
+ * envelope, for clouds < 1 and for another `which`. */
+SHW_API size_t shw_pose_head_workspace_bytes(long clouds, int emb, int w1, int w2, int w3, int w4, int w5, int which);
+
+/* tf, sf (clouds, emb) fp32, params -> out (clouds, 7) fp32 and `saved` (which == 2 bytes) for the backward.  One launch
+ * per layer and one that adds the last layer's partial sums.  workspace (which == 0 bytes) need not be cleared. */
+SHW_API int shw_pose_head_forward(const float* tf, const float* sf, const float* params, long clouds, int emb, int w1,
+                                  int w2, int w3, int w4, int w5, float* out, float* saved, void* workspace, void* stream);
+
+/* gout (clouds, 7): gradient w.r.t. out; saved as the forward wrote it.  gtf, gsf (clouds, emb) out, gparams out, laid
+ * out as params; each may be NULL and is then not computed.  One launch per layer (input gradient and weight gradient
+ * are workgroup ranges of one grid) and one that adds the first layer's partial sums into gtf / gsf.  workspace
+ * (which == 1 bytes) need not be cleared.
+ * (Replaces autograd's backward through `self.linear` and the `cat`.) */
+SHW_API int shw_pose_head_backward(const float* tf, const float* sf, const float* params, const float* saved,
+                                   const float* gout, long clouds, int emb, int w1, int w2, int w3, int w4, int w5,
+                                   float* gtf, float* gsf, float* gparams, void* workspace, void* stream);
+
+/* workgroups per cloud of the pose update's backward: min(ceil(points / 256), 64), 0 for points <= 0.  Workgroup x
+ * takes the 256-point tiles x, x + blocks, ... in order.  (No counterpart in the reference.) */
+SHW_API int shw_pose_update_backward_blocks(long points);
+
+/* bytes of the pose update's backward workspace: twelve partial sums per workgroup; 0 for clouds < 1 or points < 1 */
+SHW_API size_t shw_pose_update_workspace_bytes(long clouds, long points);
+
+/* vector (clouds, 7), est_R (clouds, 3, 3), est_t (clouds, 1, 3), source (clouds, points, 3), all fp32 ->
+ *     q = vector[0:4] / max(|vector[0:4]|, 1e-12),  t = vector[4:7],  rot(x) = x + 2 (q0 u x x + u x (u x x)),  u = q[1:4],
+ *     est_R_out = R est_R,  est_t_out = est_t R^T + t,  source_out[n] = rot(source[n]) + t,   R's columns rot(e_j).
+ * One launch.  The zero quaternion gives R = I. */
+SHW_API int shw_pose_update_forward(const float* vector, const float* est_R, const float* est_t, const float* source,
+                                    long clouds, long points, float* est_R_out, float* est_t_out, float* source_out,
+                                    void* stream);
+
+/* g_est_R_out, g_est_t_out, g_source_out: the cotangents of the three outputs, each may be NULL (absent).  g_vector
+ * (clouds, 7), g_est_R, g_est_t, g_source out; each may be NULL and is then not computed.  One launch over the points
+ * (g_source = R^T g and the per-workgroup sums of g and g x^T) and one lane per cloud that adds the sums in workgroup order
+ * and carries them through the rotation, the quaternion and its normalisation (F.normalize's rule: above the clamp
+ * (g - q (q . g)) / |v|, at or below it g / 1e-12).  workspace: shw_pose_update_workspace_bytes bytes, needed with
+ * g_vector and g_source_out; it need not be cleared.  No atomics: the same inputs give the same bits. */
+SHW_API int shw_pose_update_backward(const float* vector, const float* est_R, const float* est_t, const float* source,
+                                     const float* g_est_R_out, const float* g_est_t_out, const float* g_source_out,
+                                     long clouds, long points, float* g_vector, float* g_est_R, float* g_est_t,
+                                     float* g_source, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

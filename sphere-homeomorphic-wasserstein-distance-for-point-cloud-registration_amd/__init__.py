@@ -19,6 +19,8 @@ from .modules import (ChamferCriterion, GraphedAscent, GraphedStep, SlicedSphere
 from .pcrnet import (MLP_Architecture, PCRNet, Pooling, convert2transformation, create_pose_7d, get_quaternion,
                      get_translation, pointnet_max_features, pointnet_max_features_composed, pointnet_param_count,
                      pointnet_supported, qrot, quaternion_rotate, quaternion_transform, unpack_pointnet_params)
+from .pose import (pose_head, pose_head_composed, pose_head_param_count, pose_head_supported, pose_update,
+                   pose_update_composed, unpack_pose_head_params)
 from .sinkhorn import (log_N_Sinkhorn_Distance_Loss, log_Sinkhorn_Distance_Loss, sinkhorn_barycentric_map,
                        sinkhorn_pair_costs)
 from .sphere_map import sphere_map, sphere_map_composed, transform_to_sphere, transform_to_sphere_fast
@@ -41,4 +43,5 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "Pooling", "convert2transformation", "create_pose_7d", "get_quaternion", "get_translation",
            "pointnet_max_features", "pointnet_max_features_composed", "pointnet_param_count", "pointnet_supported", "qrot",
            "quaternion_rotate", "quaternion_transform", "unpack_pointnet_params", "sphere_map", "sphere_map_composed",
-           "transform_to_sphere", "transform_to_sphere_fast"]
+           "transform_to_sphere", "transform_to_sphere_fast", "pose_head", "pose_head_composed", "pose_head_param_count",
+           "pose_head_supported", "pose_update", "pose_update_composed", "unpack_pose_head_params"]

@@ -215,6 +215,20 @@ _SIGNATURES = {
     "shw_sphere_map_forward": (ctypes.c_int, [_c_f32p, _c_f32p, ctypes.c_long, _c_f32p, ctypes.c_void_p]),
     "shw_sphere_map_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long, _c_f32p, _c_f32p, _c_f32p,
                                                ctypes.c_void_p]),
+    # the registration network after its trunk (csrc/shw_pose.hip): the pose head's six linear layers, the pose update
+    "shw_pose_head_supported": (ctypes.c_int, [ctypes.c_int] * 6),
+    "shw_pose_head_param_count": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "shw_pose_head_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long] + [ctypes.c_int] * 7),
+    "shw_pose_head_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long] + [ctypes.c_int] * 6
+                              + [_c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "shw_pose_head_backward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long]
+                               + [ctypes.c_int] * 6 + [_c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "shw_pose_update_backward_blocks": (ctypes.c_int, [ctypes.c_long]),
+    "shw_pose_update_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
+    "shw_pose_update_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, _c_f32p,
+                                               _c_f32p, _c_f32p, ctypes.c_void_p]),
+    "shw_pose_update_backward": (ctypes.c_int, [_c_f32p] * 7 + [ctypes.c_long, ctypes.c_long] + [_c_f32p] * 4
+                                 + [ctypes.c_void_p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

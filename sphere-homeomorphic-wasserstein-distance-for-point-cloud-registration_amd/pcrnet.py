@@ -261,11 +261,21 @@ class PCRNet(nn.Module):
     when the class is defined and shared by every model built without the argument; here each model gets its own.
 
     The trunk runs through `feature_model.pooled` (fused on the device) with the parameters packed once per forward,
-    not once per trunk call; a feature model without `pooled` runs as `Pooling()(feature_model(x))`.  The head and the
-    pose update are torch."""
+    not once per trunk call; a feature model without `pooled` runs as `Pooling()(feature_model(x))`.
 
-    def __init__(self, feature_model=None, droput=0.0):
+    The head and the pose update are torch unless asked for: `fused_head` and `fused_update` (attributes, and keyword
+    arguments after `droput`; both False by default) send them through `pose_head` and `pose_update` (pose.py,
+    csrc/shw_pose.hip) when the tensors are float32 on the device and, for the head, `linear` is the dropout-free stack
+    Linear, ReLU x 5, Linear -> 7 with widths inside the kernel's envelope; the head's parameters are then packed once
+    per forward.  Anywhere else -- the CPU, float64, `droput > 0`, a `linear` edited to other shapes -- a set flag runs
+    `linear` itself and `pose_update_composed`, which are today's operations.  With both flags False the lines below are
+    the only ones that run."""
+
+    def __init__(self, feature_model=None, droput=0.0, fused_head=False, fused_update=False):
         super().__init__()
+        self.fused_head = fused_head
+        self.fused_update = fused_update
+        self._packed_head = None
         self.feature_model = MLP_Architecture() if feature_model is None else feature_model
         self.pooling = Pooling()
         emb = self.feature_model.emb_dims
@@ -282,7 +292,52 @@ class PCRNet(nn.Module):
             return self.feature_model.pooled(points, packed)
         return self.pooling(self.feature_model(points))
 
+    def head_shape(self):
+        """(emb, the five hidden widths) when `linear` is the stack the fused head computes, else None"""
+        mods = list(self.linear)
+        linears, relus = mods[0::2], mods[1::2]
+        if (len(mods) != 11 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in linears)
+                or not all(isinstance(m, nn.ReLU) for m in relus)):
+            return None
+        if (linears[0].in_features % 2 or linears[-1].out_features != 7
+                or any(a.out_features != b.in_features for a, b in zip(linears, linears[1:]))):
+            return None
+        return linears[0].in_features // 2, tuple(m.out_features for m in linears[:-1])
+
+    def packed_head_params(self):
+        """the head kernels' parameter buffer: W1, b1, ..., W6, b6 of `linear` in one `torch.cat`, differentiable w.r.t. each"""
+        return torch.cat([t.reshape(-1) for m in self.linear if isinstance(m, nn.Linear) for t in (m.weight, m.bias)])
+
+    def uses_fused_head(self, template_features):
+        from . import pose
+        shape = self.head_shape()
+        t = template_features
+        return (self.fused_head and shape is not None and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2
+                and t.shape[0] >= 1 and t.shape[1] == shape[0] and pose.pose_head_supported(*shape)
+                and self.linear[0].weight.dtype == torch.float32 and self.linear[0].weight.device == t.device)
+
+    def uses_fused_update(self, vector, source):
+        from . import pose
+        return (self.fused_update and source.is_cuda and source.dtype == torch.float32 and vector.dtype == torch.float32
+                and source.dim() == 3 and 1 <= source.shape[0] <= pose.MAX_CLOUDS and source.shape[1] >= 1
+                and source.shape[2] == 3)
+
+    def _pose_estimation_switched(self, template_features, source, est_R, est_t, packed=None):
+        """Pose_estimation with a flag set: each half through its fused op where that applies, else as below"""
+        from . import pose
+        self.source_features = self.features(source, packed)
+        if self.uses_fused_head(template_features):
+            packed_head = self.packed_head_params() if self._packed_head is None else self._packed_head
+            vector = pose.pose_head(template_features, self.source_features, packed_head, self.head_shape()[1])
+        else:
+            vector = self.linear(torch.cat([template_features, self.source_features], dim=1))
+        if self.uses_fused_update(vector, source):
+            return pose.pose_update(vector, est_R, est_t, source)
+        return pose.pose_update_composed(vector, est_R, est_t, source)
+
     def Pose_estimation(self, template_features, source, est_R, est_t, packed=None):
+        if self.fused_head or self.fused_update:
+            return self._pose_estimation_switched(template_features, source, est_R, est_t, packed)
         batch_size = source.size(0)
         self.source_features = self.features(source, packed)
         pose_7d = create_pose_7d(self.linear(torch.cat([template_features, self.source_features], dim=1)))
@@ -300,8 +355,11 @@ class PCRNet(nn.Module):
         est_t = torch.zeros(1, 3).to(template).view(1, 1, 3).expand(batch_size, 1, 3).contiguous()
         packed = self.feature_model.packed_params() if hasattr(self.feature_model, "packed_params") else None
         template_features = self.features(template, packed)
+        if self.fused_head and self.uses_fused_head(template_features):
+            self._packed_head = self.packed_head_params()              # once per forward, as the trunk's
         for _ in range(int(iteration_num)):
             est_R, est_t, source = self.Pose_estimation(template_features, source, est_R, est_t, packed)
+        self._packed_head = None
         return {"est_R": est_R, "est_t": est_t, "est_T": convert2transformation(est_R, est_t),
                 "r": template_features - self.source_features, "transformed_source": source}
 
