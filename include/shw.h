@@ -917,6 +917,58 @@ SHW_API int shw_pose_update_backward(const float* vector, const float* est_R, co
                                      long clouds, long points, float* g_vector, float* g_est_R, float* g_est_t,
                                      float* g_source, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The sphere encoder of the minibatch Residual-MSSW loss with its blocks applied forward (csrc/shw_mssw.hip).
+ * Replaces: the values and gradients of `transform_to_sphere(flow_name="Residual", n_flow_layer)` of
+ * mini_batch_Residual_MSSW.py:392-406 after its data-dependent initialisation -- the pointwise encoder
+ * `MLP_Architecture` (:327-355), the flows of `Flow_structure` (:359-390) and the angle map (:402-404) -- with every
+ * `Residual` built with reverse=False.  (The file itself leaves the class's default reverse=True, which applies each
+ * block as its inverse by a fixed-point loop that stops on a test over the whole batch: no per-point kernel; mssw.py runs
+ * it composed.)  Per point (b, n) of a (B, N, 3) cloud:
+ *     h1 = relu(W1 x + b1) (8),  h2 = relu(W2 h1 + b2) (8),  z = W3 h2 + b3 (2),
+ *     per flow f:  z <- z + W_eff,1 a(W_eff,0 a(z) + c0) + c1,   z <- z * exp(s[f, n]) + t[f, n],
+ *     theta1 = pi (tanh(z0) / 2 + 1/2),  theta2 = pi tanh(z1),
+ *     y = (sin theta1 cos theta2, sin theta1 sin theta2, cos theta1),
+ * a(x) = x sigmoid(gamma x) / 1.1.  The scale and shift are per POINT INDEX n and coordinate: the reference's ActNorm(2)
+ * takes its statistics over the batch axis only.
+ * PARAMETERS are one flat fp32 buffer: W1 row-major (8, 3), b1 (8), W2 (8, 8), b2 (8), W3 (2, 8), b3 (2) -- 122 floats, the
+ * encoder in state-dict order -- then per flow gamma0 = softplus(beta0), W_eff,0 (4, 2), c0 (4), gamma1, W_eff,1 (2, 4),
+ * c1 (2) -- 24 floats, W_eff = W / max(1, sigma / 0.9) formed by the caller.  AFFINE is (flows, N, 4) fp32, 16-byte
+ * aligned: (s0, s1, t0, t1) per flow and point index.
+ * ENVELOPE: points of dimension 3, hidden == 4, layers == 2, 1 <= flows <= 8.  The ReLU slope is pre > 0.  Anything else
+ * is hipErrorInvalidValue, returned before any HIP call.  No entry allocates, synchronises or reads back; all can be
+ * captured into a graph.
+ */
+
+/* 1 for hidden == 4, layers == 2, 1 <= flows <= 8, else 0.  Makes no HIP call.  (Replaces the widths written into
+ * :373-374.) */
+SHW_API int shw_mssw_supported(int hidden, int layers, int flows);
+
+/* floats of the parameter buffer, 122 + 24 flows; 0 outside the envelope */
+SHW_API size_t shw_mssw_param_count(int flows);
+
+/* workgroups (one wave each) the backward launches for `points` = B N points: min(ceil(points / 64), 1024), 0 for
+ * points <= 0.  Workgroup b takes the 64-point tiles b, b + blocks, ... in order.  (No counterpart in the reference.) */
+SHW_API int shw_mssw_backward_blocks(long points);
+
+/* bytes of the backward's workspace: B N flows 16-byte groups (every point's own scale and shift gradients) and one
+ * (122 + 24 flows)-float partial vector per workgroup; 0 for B N <= 0 and outside the envelope */
+SHW_API size_t shw_mssw_workspace_bytes(long B, long N, int flows);
+
+/* x (B, N, 3) fp32, params, affine -> y (B, N, 3) fp32, unit vectors.  One launch.  B N == 0 is a no-op.
+ * (Replaces `forward`, :398-406.) */
+SHW_API int shw_mssw_forward(const float* x, const float* params, const float* affine, long B, long N, int flows, float* y,
+                             void* stream);
+
+/* gy (B, N, 3): gradient w.r.t. y.  gx (B, N, 3) out, gparams (122 + 24 flows) out, gaffine (flows, N, 4) out (16-byte
+ * aligned), laid out as the inputs; each may be NULL and is then not computed.  Nothing is saved by the forward: all is
+ * recomputed from x.  gaffine[f, n] sums over the batch axis only, in ascending b; gparams sums over all points, in a
+ * fixed order; no atomics: the same inputs give the same bits.  workspace: shw_mssw_workspace_bytes bytes, 16-byte
+ * aligned, needed with gparams or gaffine; it need not be cleared.  B N == 0 zeroes gparams and gaffine.
+ * (Replaces autograd's backward through :399-404, reached from `loss.backward(retain_graph=True)`, :440.) */
+SHW_API int shw_mssw_backward(const float* x, const float* params, const float* affine, const float* gy, long B, long N,
+                              int flows, float* gx, float* gparams, float* gaffine, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,9 +13,13 @@ from .flows import (Norm_Flow_structure, Norm_Flow_structure_optuna, residual_fl
 from .gsw import (GSWD_circular, GSWD_polynomial, cosine_distance_torch, distributional_sliced_wasserstein_distance,
                   gsw_circular_slice_sums, gsw_nn_1, gsw_nn_3, gsw_polynomial_slice_sums, max_GSWD_circular,
                   max_GSWD_polynomial_3, max_GSWD_polynomial_5, max_gsw_nn_1, max_gsw_nn_3, poly_degree, sorted_row_sums)
+from . import mssw
 from .line_ot import esw_slice_costs, line_ot_rows, weighted_sliced_wasserstein_distance
 from .modules import (ChamferCriterion, GraphedAscent, GraphedStep, SlicedSphereW, SSWCriterion, max_cos_disimilarity_wassersten_distance,
                       max_spherical_wassersten_distance, max_spherical_wassersten_distance_fast)
+from .mssw import (ActNorm, Flow_structure, max_spherical_wassersten_distance_Residual, residual_sphere_map,
+                   residual_sphere_map_composed)
+from .mssw import transform_to_sphere as transform_to_sphere_Residual
 from .pcrnet import (MLP_Architecture, PCRNet, Pooling, convert2transformation, create_pose_7d, get_quaternion,
                      get_translation, pointnet_max_features, pointnet_max_features_composed, pointnet_param_count,
                      pointnet_supported, qrot, quaternion_rotate, quaternion_transform, unpack_pointnet_params)
@@ -44,4 +48,6 @@ __all__ = ["_lib", "dist", "binary_search_circle", "circle_coordinates", "emd1D_
            "pointnet_max_features", "pointnet_max_features_composed", "pointnet_param_count", "pointnet_supported", "qrot",
            "quaternion_rotate", "quaternion_transform", "unpack_pointnet_params", "sphere_map", "sphere_map_composed",
            "transform_to_sphere", "transform_to_sphere_fast", "pose_head", "pose_head_composed", "pose_head_param_count",
-           "pose_head_supported", "pose_update", "pose_update_composed", "unpack_pose_head_params"]
+           "pose_head_supported", "pose_update", "pose_update_composed", "unpack_pose_head_params", "mssw",
+           "max_spherical_wassersten_distance_Residual", "Flow_structure", "ActNorm", "transform_to_sphere_Residual",
+           "residual_sphere_map", "residual_sphere_map_composed"]

@@ -229,6 +229,16 @@ _SIGNATURES = {
                                                _c_f32p, _c_f32p, ctypes.c_void_p]),
     "shw_pose_update_backward": (ctypes.c_int, [_c_f32p] * 7 + [ctypes.c_long, ctypes.c_long] + [_c_f32p] * 4
                                  + [ctypes.c_void_p, ctypes.c_void_p]),
+    # the sphere encoder of the minibatch Residual-MSSW loss (csrc/shw_mssw.hip): ReLU encoder, i-ResNet flows with a
+    # per-point-index scale and shift, angle map
+    "shw_mssw_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "shw_mssw_param_count": (ctypes.c_size_t, [ctypes.c_int]),
+    "shw_mssw_backward_blocks": (ctypes.c_int, [ctypes.c_long]),
+    "shw_mssw_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long, ctypes.c_int]),
+    "shw_mssw_forward": (ctypes.c_int, [_c_f32p, _c_f32p, _c_f32p, ctypes.c_long, ctypes.c_long, ctypes.c_int, _c_f32p,
+                                        ctypes.c_void_p]),
+    "shw_mssw_backward": (ctypes.c_int, [_c_f32p] * 4 + [ctypes.c_long, ctypes.c_long, ctypes.c_int] + [_c_f32p] * 3
+                          + [ctypes.c_void_p, ctypes.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
